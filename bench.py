@@ -3,13 +3,20 @@
 A "step" is one full style-transfer forward — vit_c(content), vit_s(style),
 adaFormer(fc, fs) (infer_image.py:83-85 / infer_time.py:74-77) — over one synthetic batch
 already resident in HBM.  Headline workload = BASELINE configs[1]: 512x512, batch 8, fp32.
-The line also carries configs[2] (1024x1024, batch 4, bf16 MFMA path), configs[3] (the
+A plain run sets up, warms up, times the K steps of that workload and prints the result line.
+With --full the line also carries the headline's attention roofline and the shader clock, and under
+"configs" configs[2] (1024x1024, batch 4, bf16 MFMA path), configs[3] (the
 train_image.py step at 512x512, 8 images per GPU), configs[4] (1080p u8 video frames ingested,
 stylised against a cached 256^2 style + warping error, fp32 and bf16) and the reference's own
-latency probe (infer_time.py: B=1 512^2, eager and hipGraph-replayed) under "configs".
+latency probe (infer_time.py: B=1 512^2, eager and hipGraph-replayed), and the CPU baseline.
 
-  python bench.py [--gpus N --steps K --warmup W]
+  python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]
   torchrun --nproc-per-node N bench.py --gpus N ...   (one process per GPU)
+
+--dump-outputs DIR: after the timed steps rank 0 writes what the last timed step returned as
+DIR/<name>.npy (float32; the headline: fcs, cs; --train: losses, float64), under 64 MB in all: an
+array over its share is written as a fixed seeded sample of its elements.  Inputs and weights are
+seeded, so two runs with the same arguments dump comparable arrays.
 
 --gpus N > 1 without a launcher (WORLD_SIZE unset): bench.py starts the N rank processes itself
 (one child per GPU, RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set, 127.0.0.1 rendezvous) BEFORE
@@ -20,13 +27,13 @@ Multi-GPU: inference replicas: the ViT's batch-axis attention c
 images of one forward call, so a call's batch is never split; each rank runs its own batch,
 no collective on the data path (barrier + max-over-ranks timing only) -> scaling "weak".
 
-Roofline: the dominant kernel is the fused MHAda attention (6 launches/step); its algorithmic FLOPs
+Roofline (--full): the dominant kernel is the fused MHAda attention (6 launches/step); its algorithmic FLOPs
 per launch = 6*Nc*Ns*C*B (QK^T, PV, PV^2; 2 FLOP/MAC), timed live with HIP events on its launch
 stream over the timed region.  The fp32 headline's attention (mhada_attn_split3) runs fp32-accurate
 SPLIT3 products on the bf16 MFMA, so its line prices the bf16 MFMA FLOPs it issues (6.25x the
 algorithmic fp32 FLOPs) against the bf16 peak and states the fp32-equivalent rate beside them.  After every timed region the same process
 runs a shader-clock probe (csrc/probe.hip) and reports the box's clock under dense MFMA load
-("clock_ghz"; "frac_at_clock" = the fraction of the peak scaled to that clock).  CPU baseline (rank 0, N=1): the
+("clock_ghz"; "frac_at_clock" = the fraction of the peak scaled to that clock).  CPU baseline (--full; rank 0, N=1): the
 reference's aten fp32 expression (tests/torch_ref.py, golden-pinned) at B=1 on the job's host
 cores, with the numpy oracle beside it.
 """
@@ -165,7 +172,10 @@ def build_models(dtype):
     return vc, vs, ada
 
 
-def run_config(res, batch, dtype, steps, warmup, rank, world):
+def run_config(res, batch, dtype, steps, warmup, rank, world, full=True):
+    """One inference config.  ``full``: also bracket the attention launches with HIP events inside
+    the timed region and run the shader-clock probe after it (roofline, clock_ghz); a plain run
+    times the steps alone.  "outputs" holds what the last timed step returned."""
     from mhada_hip import engine
     from mhada_hip.recipe import seeded_image
     vc, vs, ada = build_models(dtype)
@@ -186,7 +196,8 @@ def run_config(res, batch, dtype, steps, warmup, rank, world):
             dist.barrier()
         torch.cuda.synchronize()
         log = {}
-        engine.record_kernel_events(log)
+        if full:
+            engine.record_kernel_events(log)
         t0 = time.perf_counter()
         with _mark(f"{res}x{res}_b{batch}_{'f32' if dtype == torch.float32 else 'bf16'}", steps):
             for _ in range(steps):
@@ -198,15 +209,33 @@ def run_config(res, batch, dtype, steps, warmup, rank, world):
         elapsed = time.perf_counter() - t0
         engine.record_kernel_events(None)
     assert torch.isfinite(out[1]).all()
-    clock = shader_clock()
-    ev = log.get("mhada_attn", [])
-    attn_ms = [a.elapsed_time(b) for a, b in ev]
+    clock = shader_clock() if full else None
     elapsed = max_over_ranks(elapsed, world)
     frames = batch * steps * world
     dts = "f32" if dtype == torch.float32 else "bf16"
     fl = flops_per_frame(res, res)
+    r = {
+        "value": frames / elapsed,
+        "ms_per_step": elapsed / steps * 1e3,
+        "dtype": dts,
+        "frames_per_s_per_gpu": frames / elapsed / world,
+        "tflops_whole_step": fl["total"] * batch * steps / (elapsed) / 1e12,
+        "config": {"workload": f"stylize {res}x{res} content+style, batch {batch}", "resolution": res,
+                   "batch_per_gpu": batch, "global_batch": batch * world, "compute_dtype": dts,
+                   "parallelism": f"replicas x{world}"},
+        "outputs": {"fcs": out[0], "cs": out[1]},
+    }
+    if full:
+        attn_ms = [a.elapsed_time(b) for a, b in log.get("mhada_attn", [])]
+        r["roofline"] = attn_roofline(res, batch, dtype, attn_ms, fl["attn_per_block"] * batch, clock)
+        r["clock_ghz"] = clock
+    return r
+
+
+def attn_roofline(res, batch, dtype, attn_ms, attn_flops, clock):
+    """The attention kernel's roofline entry from its event-timed launches (ms) of one timed region."""
+    dts = "f32" if dtype == torch.float32 else "bf16"
     avg_attn_s = (sum(attn_ms) / len(attn_ms)) / 1e3 if attn_ms else float("nan")
-    attn_flops = fl["attn_per_block"] * batch
     traffic, tsrc = pmc_traffic(f"{res}x{res}_b{batch}_{dts}")
     from mhada_hip import ops
     split3 = dtype == torch.float32 and ops.F32_SPLIT_ATTN
@@ -229,18 +258,32 @@ def run_config(res, batch, dtype, steps, warmup, rank, world):
         roof["algorithmic_fp32_flop_per_launch"] = attn_flops
         roof["fp32_equiv_tflops"] = round(attn_flops / avg_attn_s / 1e12, 2)
         roof["fp32_equiv_frac_of_fp32_peak"] = round(attn_flops / avg_attn_s / 1e12 / PEAK_TFLOPS["f32"], 4)
-    return {
-        "value": frames / elapsed,
-        "ms_per_step": elapsed / steps * 1e3,
-        "dtype": dts,
-        "frames_per_s_per_gpu": frames / elapsed / world,
-        "tflops_whole_step": fl["total"] * batch * steps / (elapsed) / 1e12,
-        "roofline": roof,
-        "clock_ghz": clock,
-        "config": {"workload": f"stylize {res}x{res} content+style, batch {batch}", "resolution": res,
-                   "batch_per_gpu": batch, "global_batch": batch * world, "compute_dtype": dts,
-                   "parallelism": f"replicas x{world}"},
-    }
+    return roof
+
+
+DUMP_BUDGET_BYTES = 60 * 10 ** 6  # --dump-outputs: every array of one dump together (limit: 64 MB)
+
+
+def dump_outputs(out_dir, arrays, budget=DUMP_BUDGET_BYTES):
+    """--dump-outputs: write each tensor of ``arrays`` ({name: tensor}) as <out_dir>/<name>.npy,
+    float64 as it is and every other dtype as float32.  Each array gets an equal share of ``budget``
+    bytes; one that fits is written whole in its own shape, a larger one as a 1-D stratified sample
+    in element order: one element out of every ``stride`` consecutive ones (row-major), at an offset
+    drawn from a generator seeded with 0 — the same elements in every run and every build."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    share = budget // len(arrays)
+    for name, t in arrays.items():
+        t = t.detach()
+        t = t if t.dtype == torch.float64 else t.float()
+        n = share // t.element_size()
+        if t.numel() > n:
+            stride = -(-t.numel() // n)
+            count = t.numel() // stride
+            g = torch.Generator(device="cpu").manual_seed(0)
+            idx = torch.arange(count) * stride + torch.randint(0, stride, (count,), generator=g)
+            t = t.reshape(-1)[idx.to(t.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy())
 
 
 def run_video(dtype, steps, warmup, rank, world):
@@ -567,16 +610,23 @@ def main():
                     help="ranks (one per GPU); > 1 without a launcher starts the ranks itself")
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the 1024^2 bf16 config")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: its attention roofline and shader clock, "
+                         "the 1024^2 bf16, video, training and latency configs, the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (under 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="--full without the configs beside the headline")
     ap.add_argument("--only-secondary", action="store_true", help="run only the 1024^2 bf16 config (profiling)")
     ap.add_argument("--train", action="store_true", help="only BASELINE configs[3]: DP training step at 512^2")
-    ap.add_argument("--no-train", action="store_true", help="skip the training config in the default line")
+    ap.add_argument("--no-train", action="store_true", help="--full without the training config")
     ap.add_argument("--device", choices=("cuda", "cpu"), default="cuda",
                     help="cpu: rehearse the rank protocol on the CPU (--train only, gloo; tests)")
     ap.add_argument("--train-res", type=int, default=512, help=argparse.SUPPRESS)
     ap.add_argument("--train-batch", type=int, default=8, help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ:
         if args.gpus is not None and args.gpus > 1:
@@ -608,6 +658,10 @@ def main():
     if args.train:
         r = run_train(args.steps, args.warmup, rank, world, args.train_res, args.train_batch)
         if rank == 0:
+            if args.dump_outputs:
+                losses = r["last_losses"]
+                dump_outputs(args.dump_outputs,
+                             {"losses": torch.tensor([losses[k] for k in sorted(losses)], dtype=torch.float64)})
             print(json.dumps(r), flush=True)
         if world > 1:
             dist.barrier()
@@ -615,10 +669,19 @@ def main():
         return
     if args.only_secondary:
         r = run_config(1024, 4, torch.bfloat16, args.steps, args.warmup, rank, world)
+        outputs = r.pop("outputs")
         if rank == 0:
+            if args.dump_outputs:
+                dump_outputs(args.dump_outputs, outputs)
             print(json.dumps(r), flush=True)
         return
-    main_cfg = run_config(512, 8, torch.float32, args.steps, args.warmup, rank, world)
+    main_cfg = run_config(512, 8, torch.float32, args.steps, args.warmup, rank, world, full=args.full)
+    outputs = main_cfg.pop("outputs")
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, outputs)
+    del outputs
+    if not args.full:  # a plain run: the headline alone
+        args.no_secondary = args.no_cpu_baseline = True
     second = None if args.no_secondary else run_config(1024, 4, torch.bfloat16, args.steps, args.warmup, rank, world)
     videos = {} if args.no_secondary else {
         f"video_1080p_s256_{'f32' if dt == torch.float32 else 'bf16'}": run_video(dt, args.steps, args.warmup, rank, world)
@@ -644,10 +707,11 @@ def main():
             "dtype": main_cfg["dtype"],
             "data": "synthetic rand*255 images, recipe random-init weights (no checkpoint ships)",
             "config": main_cfg["config"],
-            "roofline": main_cfg["roofline"],
             "tflops_whole_step": round(main_cfg["tflops_whole_step"], 2),
-            "clock_ghz": main_cfg["clock_ghz"],
         }
+        if args.full:
+            line["roofline"] = main_cfg["roofline"]
+            line["clock_ghz"] = main_cfg["clock_ghz"]
         if second is not None:
             line["configs"] = {"1024x1024_b4_bf16": {k: second[k] for k in
                                                     ("value", "ms_per_step", "frames_per_s_per_gpu", "dtype",

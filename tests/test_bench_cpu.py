@@ -9,7 +9,9 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
+import torch
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -31,8 +33,8 @@ def _json_lines(out):
 SMALL = ["--train", "--device", "cpu", "--train-res", "64", "--train-batch", "2", "--steps", "1", "--warmup", "0"]
 
 
-def test_gpus_2_self_launches_two_ranks():
-    p = _run(["--gpus", "2"] + SMALL)
+def test_gpus_2_self_launches_two_ranks(tmp_path):
+    p = _run(["--gpus", "2", "--dump-outputs", str(tmp_path)] + SMALL)
     assert p.returncode == 0, p.stderr[-4000:]
     lines = _json_lines(p.stdout)
     assert len(lines) == 1, p.stdout  # rank 0 only
@@ -42,6 +44,11 @@ def test_gpus_2_self_launches_two_ranks():
     ag = r["rank_agreement"]
     assert ag["identical"] and ag["world"] == 2 and ag["backend"] == "gloo", ag
     assert all(v == v for v in r["last_losses"].values())  # finite (not NaN)
+    # --dump-outputs: rank 0 alone wrote the last step's losses, float64, in sorted key order
+    assert sorted(os.listdir(tmp_path)) == ["losses.npy"]
+    dumped = np.load(tmp_path / "losses.npy")
+    assert dumped.dtype == np.float64
+    assert dumped.tolist() == [r["last_losses"][k] for k in sorted(r["last_losses"])]
 
 
 def test_world_size_must_match_gpus():
@@ -63,3 +70,30 @@ def test_failing_rank_fails_the_job():
 def test_cpu_device_is_training_only(argv):
     p = _run(argv, timeout=120)
     assert p.returncode != 0
+
+
+def test_dump_outputs_whole_and_sampled(tmp_path):
+    """bench.dump_outputs: an array within its share of the budget is written whole (float32, its
+    own shape), a larger one as the same stratified sample in every call, and the files together
+    stay within the budget."""
+    sys.path.insert(0, REPO)
+    import bench
+    g = torch.Generator().manual_seed(3)
+    small = torch.rand(2, 3, 5, 7, generator=g).to(torch.bfloat16)
+    big = torch.rand(4, 1001, 13, generator=g)  # 52052 elements, no multiple of the stride
+    f64 = torch.rand(9, generator=g, dtype=torch.float64)
+    budget = 3 * 4 * 6000  # share: 6000 float32 elements per array -> stride 9, 5783 samples of big
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"small": small, "big": big, "f64": f64}, budget=budget)
+    a = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in ("small", "big", "f64")}
+    assert a["small"].dtype == np.float32 and a["small"].shape == (2, 3, 5, 7)
+    assert np.array_equal(a["small"], small.float().numpy())
+    assert a["f64"].dtype == np.float64 and np.array_equal(a["f64"], f64.numpy())
+    assert a["big"].dtype == np.float32 and a["big"].shape == (52052 // 9,)
+    # one element of every 9 consecutive ones, in order
+    flat = big.reshape(-1).numpy()
+    blocks = flat[: 5783 * 9].reshape(5783, 9)
+    assert (blocks == a["big"][:, None]).any(axis=1).all()
+    assert not np.array_equal(a["big"], blocks[:, 0])  # seeded offsets, not a plain stride
+    assert np.array_equal(a["big"], np.load(tmp_path / "b" / "big.npy"))
+    assert sum(os.path.getsize(tmp_path / "a" / f) - 128 for f in os.listdir(tmp_path / "a")) <= budget

@@ -1,6 +1,6 @@
 """Average duration of the MHAda attention kernel per bench config from a rocprofv3
-kernel_trace.csv of the default bench command (configs told apart by grid size), to set beside
-the bench line's roofline.avg_launch_ms (HIP events on the launch stream).
+kernel_trace.csv of `bench.py --full` (configs told apart by grid size), to set beside
+that bench line's roofline.avg_launch_ms (HIP events on the launch stream).
 
 usage: python tools/attn_grid_stats.py <run_kernel_trace.csv>
 """

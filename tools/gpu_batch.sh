@@ -4,7 +4,7 @@
 #   c64        decoder conv3.0 fused vs split upsample (tools/c64_ab.py)
 #   newtests   the round-4 GPU tests (ingest, graphs, training forward / folds / 512^2 B1 losses)
 #   gpu        the whole pytest -m gpu suite
-#   bench      the default bench line
+#   bench      the full bench line (bench.py --full)
 #   trainclock in-kernel clock of the training dK/dV' kernel (diagnostic build)
 #   vit        the ViT / batched-training tests (LinearFn residual, batched ViT / AdaFormer, goldens)
 #   winotests / winoab  the Winograd conv tests / knob A/B (WINO_KNOB, default wino4)
@@ -47,7 +47,7 @@ for s in "$@"; do
     # test FAILURES (pytest rc 1) do not stop the batch; a crash, fault or time-out (any other rc) does
     newtests) timeout -k 10 900 $PYT tests/test_ingest.py tests/test_gpu_parity.py tests/test_gpu_train_attn.py tests/test_gpu_train_ops.py tests/test_gpu_train.py tests/test_gpu_kernels.py -k "ingest or graphed or default_path or full_size or fwd_kernels or chain or vgg19_and_decoder or 512_b1 or golden or n64 or bit_identical or feature_loss or mlp_relu or tile_counts or late_max" > $OUT/new_tests.log 2>&1; rc=$?; [ $rc -le 1 ] || exit 3 ;;
     gpu) timeout -k 10 1000 $PYT tests > $OUT/gpu_tests.log 2>&1; rc=$?; [ $rc -le 1 ] || exit 4 ;;
-    bench) timeout -k 10 600 python -u bench.py > $OUT/bench.log 2>&1 || exit 5 ;;
+    bench) timeout -k 10 600 python -u bench.py --full > $OUT/bench.log 2>&1 || exit 5 ;;
   esac
 done
 echo "gpu_batch $TAG done"

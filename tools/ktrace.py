@@ -1,4 +1,4 @@
-"""Per-config kernel time breakdown from a rocprofv3 kernel_trace.csv of bench.py (--no-train).
+"""Per-config kernel time breakdown from a rocprofv3 kernel_trace.csv of bench.py (--full --no-train).
 
 usage: python tools/ktrace.py <run_kernel_trace.csv> [min_ms_per_step] [--markers=<run_marker_api_trace.csv>]
                               [--bench=<stdout of the profiled bench.py>]
