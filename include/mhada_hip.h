@@ -51,7 +51,7 @@ enum {
  * p0 = bf16(y), p1 = bf16(y - p0), p2 = bf16(y - p0 - p1) of the fp32 result y (ABI 15) */
 enum { MHADA_BF16X3 = 2 };
 
-int mhada_abi_version(void);  /* 16 (mhada_split3_kv / mhada_attn_split3; 15: mhada_gemm a_mode MHADA_A_SPLIT3, mhada_layernorm y_dtype MHADA_BF16X3; 14: mhada_cosine_moments / mhada_cosine_attn, mhada_warp_bwd; 13: mhada_clock_probe; tuning knobs of removed kernel variants dropped, attn_waves 0 = auto; 12: mhada_feat_stats; 11: mhada_transpose64; 10: mhada_attn_train_fwd_vt; 9: 3-channel conv adjoints mhada_vgg_stem_dgrad / mhada_out3_dgrad / mhada_out3_wgrad; 8: mhada_feat_loss_bwd; 7: gemm c2 / vt outputs, instnorm / attention backward helpers; 6: LayerNorm / pos-embed training adjoints; 5: Winograd conv; 4: training CONV3X3_ZERO, mhada_gemm_tn, backward helpers) */
+int mhada_abi_version(void);  /* 17 (mhada_wino_weights_split3 / mhada_conv3x3_wino_split3, knob wino_split3; 16: mhada_split3_kv / mhada_attn_split3; 15: mhada_gemm a_mode MHADA_A_SPLIT3, mhada_layernorm y_dtype MHADA_BF16X3; 14: mhada_cosine_moments / mhada_cosine_attn, mhada_warp_bwd; 13: mhada_clock_probe; tuning knobs of removed kernel variants dropped, attn_waves 0 = auto; 12: mhada_feat_stats; 11: mhada_transpose64; 10: mhada_attn_train_fwd_vt; 9: 3-channel conv adjoints mhada_vgg_stem_dgrad / mhada_out3_dgrad / mhada_out3_wgrad; 8: mhada_feat_loss_bwd; 7: gemm c2 / vt outputs, instnorm / attention backward helpers; 6: LayerNorm / pos-embed training adjoints; 5: Winograd conv; 4: training CONV3X3_ZERO, mhada_gemm_tn, backward helpers) */
 const char* mhada_last_error(void);
 
 /* Kernel-variant table.  Defaults are the measured winners; the other variants serve A/B
@@ -62,7 +62,7 @@ const char* mhada_last_error(void);
  * 8-wave grid has fewer blocks than CUs), attn_tk (64|128), attn_prio (0|1), vit_attn_vec (0|1),
  * out3_mfma (0|1), out3_tile (0|1), gemm_pp (0|1), gemm_persist (0|1), gemm_pp128 (0|1),
  * gemm_ldsepi (0|1), gemm_n64 (128|256), conv_c64 (0|1), conv_dir (0|1), gemm_rinit (0|1), tn_skinny_lds (0|1),
- * train_dkv_dma (0|1), wino4 (0|1), upsample_quad (0|1; ABI 16), xknob (0..15, read by no shipped dispatch).
+ * train_dkv_dma (0|1), wino4 (0|1), wino_split3 (0|1; ABI 17), upsample_quad (0|1; ABI 16), xknob (0..15, read by no shipped dispatch).
  * Returns MHADA_ERR_ARG for an unknown knob or an out-of-range value.  No reference
  * counterpart (the reference has no kernels). */
 int mhada_set_tuning(const char* name, int value);
@@ -496,6 +496,17 @@ int mhada_conv3x3_wgrad_wino(const float* x, const float* g, float* dw, float* d
 int mhada_conv3x3_wino(const float* x, const float* u, const float* bias, float* y, int B, int H, int W,
                        int Cin, int Cout, long long ldc, int pad_mode, int pad, int relu,
                        const float* relu_mask, mhada_stream_t stream);
+/* The same conv as SPLIT3 products on the bf16 MFMA (ABI 17): every fp32 operand as three
+ * round-to-nearest bf16 planes, the six cross products with plane indices i + j <= 2 summed in
+ * fp32 (fp32-accurate, 2.67x less matrix time than the fp32 MFMA).  mhada_wino_weights_split3
+ * writes the filters' plane image up [Cin/16][16][3][Cout][16] bf16 (p0 + p1 + p2 of the u of
+ * mhada_wino_weights, 6 bytes per element; Cin % 16 == 0).  mhada_conv3x3_wino_split3 takes u AND
+ * up (16-byte aligned): it runs the SPLIT3 kernel when the knob wino_split3 is on (the default),
+ * Cin % 16 == 0 and x and up are below 2 GiB, and mhada_conv3x3_wino on u otherwise. */
+int mhada_wino_weights_split3(const float* w, void* up, int Cout, int Cin, mhada_stream_t stream);
+int mhada_conv3x3_wino_split3(const float* x, const float* u, const void* up, const float* bias, float* y, int B,
+                              int H, int W, int Cin, int Cout, long long ldc, int pad_mode, int pad, int relu,
+                              const float* relu_mask, mhada_stream_t stream);
 
 /* The 3-channel ends of the training conv stacks (rgb_ops.hip), fp32:
  * VGG19's first layer (vgg19.py:10-11,25-26: normalise -> Conv2d(3, 64, 3, padding=1) -> ReLU),

@@ -30,6 +30,8 @@
 // the transform and loads serialised with the MFMAs).  Round 5: the default is wino4_kernel
 // below (the same tile and MFMA sequence, bit-identical, 13-15 % faster); this 8-wave kernel
 // remains the fallback for inputs of 2 GiB and more (wino4 addresses x by a buffer resource).
+// Round 7: with the filters' plane image and Cin % 16 == 0 the default is wino_s3_kernel (SPLIT3
+// products on the bf16 MFMA, below); wino4_kernel and wino_kernel are unchanged.
 // LDS operand rows are 32 B (8 channels) with the two 16-B halves swapped on rows with bit 3
 // set (swz), so the ds_read_b128 of 32 consecutive rows is conflict-free; the raw patch's 16-B
 // slots are XOR-swizzled (rswz) so the transform's ds_read_b32 hit distinct banks.
@@ -527,6 +529,297 @@ __global__ void __launch_bounds__(256, 1) wino4_kernel(const WinoP p) {
   }
 }
 
+// ------------------------------------------------------------------------------------
+// SPLIT3 form (tuning wino_split3): the same workgroup tile, wave layout (one wave per SIMD, all 16
+// positions of 32 tiles x 32 channels in 256 accumulator registers), buffer-resource LDS-DMA,
+// output transform and epilogue as wino4_kernel, with the per-position channel reduction on the
+// bf16 MFMA (v_mfma_f32_32x32x16_bf16).  Each fp32 operand travels as three round-to-nearest
+// bf16 planes (x = p0 + p1 + p2, the split of mhada_layernorm BF16X3) and each product is the six
+// cross products v_i u_j with i + j <= 2, small terms first (v1u1, v2u0, v0u2, v1u0, v0u1, v0u0),
+// all into the one fp32 accumulator block: 6 MFMAs of 16 channels where the fp32 pipe needs 8 of
+// 2, 2.67x less matrix time, and the bf16 MFMA leaves vector issue slots for the transform.
+// The input channels stream in chunks of 16; a STAGE is one Winograd row (4 positions) of a chunk:
+//   * V planes [4 xi][3][64 tiles][16 ch] bf16 (24 KiB) and U planes [4 xi][3][64 co][16 ch]
+//     (24 KiB, DMA from the image of mhada_wino_weights_split3), each a two-slot ring; rows are
+//     32 B with wino_kernel's half swap (swz), so the ds_read_b128 fragment reads are conflict-free;
+//   * the raw 18 x 18-pixel fp32 patch of a chunk (64 B per pixel, 20.25 KiB), double-buffered;
+//     pixel positions permuted (rpix) so the transform's ds_read_b128 of 8 tiles of a tile row
+//     spread over the bank row.  138 KiB in all, six separate __shared__ objects (hipcc orders
+//     LDS-DMA against ds_reads by object).
+// Stage (k, i): DMA of the next stage's U planes and (i < 2) half of chunk k+1's raw patch; every
+// thread transforms row i+1 of V = B^T d B for 4 channels of one tile (row i+1 needs two raw rows;
+// fp32 adds as in wino4_kernel, then the three-way split) into the other V slot; 24 MFMAs per
+// wave on this slot; one vmcnt(0) + barrier.  Workgroups are ordered output-channel block
+// outermost, so the workgroups resident on one XCD stream one 64-channel slice of U from its L2.
+// ------------------------------------------------------------------------------------
+constexpr int kSK = 16;                          // input channels per chunk
+constexpr int kSImg = 64 * kSK * 2;              // bytes of one (position, plane) image: 64 rows x 32 B
+constexpr int kSStage = 12 * kSImg;              // a stage's V or U planes: 4 positions x 3 planes, 24 KiB
+constexpr int kSRDma = (4 * kRaw + 63) / 64;     // LDS-DMA instructions for the raw patch (21)
+constexpr int kSRawB = kSRDma * 1024;            // raw buffer bytes: 1344 16-B slots, 1296 used
+
+struct WinoS3P : WinoP {
+  const bf16* up;  // [Cin/16][16][3][Cout][16] (mhada_wino_weights_split3)
+};
+
+// LDS position of raw pixel pix (an involution): bit 0 flips with bit 2, so pixels 2 apart (the
+// tiles of a tile row) cover all four 64-B quarters of the 256-B bank row
+MHADA_DEV int rpix(int pix) { return pix ^ ((pix >> 2) & 1); }
+
+__global__ void __launch_bounds__(256, 1) wino_s3_kernel(const WinoS3P p) {
+  __shared__ __attribute__((aligned(16))) unsigned char sV0[kSStage];
+  __shared__ __attribute__((aligned(16))) unsigned char sV1[kSStage];
+  __shared__ __attribute__((aligned(16))) unsigned char sU0[kSStage];
+  __shared__ __attribute__((aligned(16))) unsigned char sU1[kSStage];
+  __shared__ __attribute__((aligned(16))) unsigned char sR0[kSRawB];
+  __shared__ __attribute__((aligned(16))) unsigned char sR1[kSRawB];
+  const int tid = threadIdx.x, lane = tid & 63, h = lane >> 5, r32 = lane & 31;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int th = wave & 1, ch = wave >> 1;
+
+  // logical block: output-channel block outermost (an XCD's contiguous id range shares a U slice)
+  int id = xcd_remap(blockIdx.x, p.nblk);
+  const int nsp = p.nblk / p.nbn;
+  const int nb = id / nsp;
+  id -= nb * nsp;
+  const int bx = id % p.nbx;
+  id /= p.nbx;
+  const int by = id % p.nby;
+  const int b = id / p.nby;
+  const int co0 = nb * kCO;
+  const int P = p.zero ? p.pad : 1;
+  const int nck = p.Cin / kSK, nst = 4 * nck;
+
+  // buffer resources (sizes < 2^31 bytes, checked on the host): offsets at or past the size read 0
+  const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(
+      const_cast<float*>(p.x), 0, (int)((long long)p.B * p.H * p.W * p.Cin * 4), 0x00020000);
+  const __amdgpu_buffer_rsrc_t ur =
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16*>(p.up), 0, p.Cin * p.Cout * 96, 0x00020000);
+  // raw patch DMA: instruction j = wave + 4 t (j < 21) fills 16-B slots 64 j + lane = pixel
+  // position (slot >> 2), channel quad (slot & 3); 0x7ff00000 (past the buffer) reads zero padding
+  int rvo[6];
+#pragma unroll
+  for (int t = 0; t < 6; ++t) {
+    const int slot = 64 * (wave + 4 * t) + lane;
+    const int pix = rpix(slot >> 2);
+    int iy = 2 * by * kT - P + pix / kRP, ix = 2 * bx * kT - P + pix % kRP;
+    bool inside = pix < kRaw;
+    if (p.zero) {
+      inside = inside && iy >= 0 && iy < p.H && ix >= 0 && ix < p.W;
+    } else {
+      iy = reflect_clamp(iy, p.H);
+      ix = reflect_clamp(ix, p.W);
+    }
+    rvo[t] = inside ? (((b * p.H + iy) * p.W + ix) * p.Cin + 4 * (slot & 3)) * 4 : 0x7ff00000;
+  }
+  // U DMA: instructions 6w .. 6w+5 of 24; slot 64 j + lane = (xi * 3 + plane, co row, stored half),
+  // the source half is the logical one (swz); byte offsets inside one stage
+  int uvo[6];
+#pragma unroll
+  for (int t = 0; t < 6; ++t) {
+    const int slot = 64 * (6 * wave + t) + lane;
+    const int g = slot >> 7, row = (slot >> 1) & 63, sh = slot & 1;
+    uvo[t] = ((g * p.Cout + co0 + row) * kSK + 8 * (sh ^ ((row >> 3) & 1))) * 2;
+  }
+  const int usb = 12 * p.Cout * kSK * 2;  // bytes per U stage
+  typedef __attribute__((address_space(3))) void* LdsP;
+
+  // transform item: channels 4 tq .. 4 tq + 3 of tile tt; LDS byte offsets of its 16 raw quads
+  const int tq = tid & 3, tt = tid >> 2;
+  int roffs[16];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) roffs[4 * i + j] = rpix((2 * (tt >> 3) + i) * kRP + 2 * (tt & 7) + j) * 64 + tq * 16;
+  const int vdst = tt * 32 + ((((tq >> 1) ^ (tt >> 3)) & 1) << 4) + (tq & 1) * 8;
+  // row I of V = (B^T d) B for the item: two raw rows, fp32 adds in wino4_kernel's association,
+  // then the three bf16 planes of each value
+  auto transform = [&](auto ic, const unsigned char* sr, unsigned char* sv) {
+    constexpr int I = decltype(ic)::value;
+    constexpr int RA = I == 0 ? 0 : (I == 2 ? 2 : 1), RB = I == 0 ? 2 : (I == 1 ? 2 : (I == 2 ? 1 : 3));
+    f32x4 t[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const f32x4 a = *reinterpret_cast<const f32x4*>(sr + roffs[4 * RA + j]);
+      const f32x4 c = *reinterpret_cast<const f32x4*>(sr + roffs[4 * RB + j]);
+      t[j] = I == 1 ? a + c : a - c;
+    }
+    const f32x4 v[4] = {t[0] - t[2], t[1] + t[2], t[2] - t[1], t[1] - t[3]};
+#pragma unroll
+    for (int x = 0; x < 4; ++x) {
+      bf16x4 p0, p1, p2;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const bf16 a = (bf16)v[x][e];
+        const float r = v[x][e] - (float)a;
+        const bf16 c = (bf16)r;
+        p0[e] = a;
+        p1[e] = c;
+        p2[e] = (bf16)(r - (float)c);
+      }
+      *reinterpret_cast<bf16x4*>(sv + (3 * x + 0) * kSImg + vdst) = p0;
+      *reinterpret_cast<bf16x4*>(sv + (3 * x + 1) * kSImg + vdst) = p1;
+      *reinterpret_cast<bf16x4*>(sv + (3 * x + 2) * kSImg + vdst) = p2;
+    }
+  };
+
+  f32x16 acc[16];
+#pragma unroll
+  for (int x = 0; x < 16; ++x)
+#pragma unroll
+    for (int q = 0; q < 16; ++q) acc[x][q] = 0.f;
+  // fragments: A rows = tiles 32 th + r32, B rows = channels 32 ch + r32; lane half h holds the
+  // row's channels 8h .. 8h+7 (one 16-B half, swz)
+  const int fsw = (h ^ ((r32 >> 3) & 1)) << 4;
+  const int aoff = (32 * th + r32) * 32 + fsw, boff = (32 * ch + r32) * 32 + fsw;
+  auto mfmas = [&](auto ic, const unsigned char* sv, const unsigned char* su) {
+    constexpr int I = decltype(ic)::value;
+    constexpr int TA[6] = {1, 2, 0, 1, 0, 0}, TB[6] = {1, 0, 2, 0, 1, 0};
+#pragma unroll
+    for (int pr = 0; pr < 2; ++pr) {  // two positions at a time: independent accumulators alternate
+      bf16x8 a[2][3], bq[2][3];
+#pragma unroll
+      for (int x = 0; x < 2; ++x)
+#pragma unroll
+        for (int pl = 0; pl < 3; ++pl) {
+          a[x][pl] = *reinterpret_cast<const bf16x8*>(sv + (3 * (2 * pr + x) + pl) * kSImg + aoff);
+          bq[x][pl] = *reinterpret_cast<const bf16x8*>(su + (3 * (2 * pr + x) + pl) * kSImg + boff);
+        }
+#pragma unroll
+      for (int t = 0; t < 6; ++t)
+#pragma unroll
+        for (int x = 0; x < 2; ++x)
+          acc[4 * I + 2 * pr + x] =
+              __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[x][TA[t]], bq[x][TB[t]], acc[4 * I + 2 * pr + x], 0, 0, 0);
+    }
+  };
+  auto publish = [&]() {
+    __builtin_amdgcn_sched_barrier(0);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+  };
+  auto dma_u = [&](int s, unsigned char* su) {
+    const int so = min(s, nst - 1) * usb;
+#pragma unroll
+    for (int t = 0; t < 6; ++t)
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(ur, (LdsP)(su + (6 * wave + t) * 1024), 16, (unsigned)uvo[t], so, 0, 0);
+  };
+  auto dma_raw = [&](int t0, int k, unsigned char* sr) {  // pieces t0 .. t0 + 2 of chunk k
+    const int so = min(k, nck - 1) * kSK * 4;
+#pragma unroll
+    for (int t = t0; t < t0 + 3; ++t)
+      if (t < 5 || wave == 0)
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(xr, (LdsP)(sr + (wave + 4 * t) * 1024), 16, (unsigned)rvo[t], so, 0, 0);
+  };
+
+  // prologue: U stage 0, raw(0); row 0 of V(0) into V slot 0
+  dma_u(0, sU0);
+  dma_raw(0, 0, sR0);
+  dma_raw(3, 0, sR0);
+  publish();
+  transform(std::integral_constant<int, 0>(), sR0, sV0);
+  __syncthreads();
+  // stage (k, I), C = k & 1: slot I & 1 holds its planes; raw(k) is in raw buffer C
+  auto stage = [&](int k, auto ic, auto cc) {
+    constexpr int I = decltype(ic)::value, C = decltype(cc)::value;
+    unsigned char* const svn = (I & 1) ? sV0 : sV1;
+    dma_u(4 * k + I + 1, (I & 1) ? sU0 : sU1);
+    if constexpr (I < 2) dma_raw(3 * I, k + 1, C ? sR0 : sR1);
+    __builtin_amdgcn_sched_barrier(0);
+    if constexpr (I < 3)
+      transform(std::integral_constant<int, I + 1>(), C ? sR1 : sR0, svn);
+    else
+      transform(std::integral_constant<int, 0>(), C ? sR0 : sR1, svn);
+    mfmas(ic, (I & 1) ? sV1 : sV0, (I & 1) ? sU1 : sU0);
+    publish();
+  };
+  auto chunk = [&](int k, auto cc) {
+    stage(k, std::integral_constant<int, 0>(), cc);
+    stage(k, std::integral_constant<int, 1>(), cc);
+    stage(k, std::integral_constant<int, 2>(), cc);
+    stage(k, std::integral_constant<int, 3>(), cc);
+  };
+  int k = 0;
+  for (; k + 1 < nck; k += 2) {
+    chunk(k, std::integral_constant<int, 0>());
+    chunk(k + 1, std::integral_constant<int, 1>());
+  }
+  if (k < nck) chunk(k, std::integral_constant<int, 0>());
+
+  // output transform and epilogue: wino4_kernel's
+  const int co = co0 + 32 * ch + r32;
+  const float bias = p.bias ? p.bias[co] : 0.f;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int tile = 32 * th + (r & 3) + 8 * (r >> 2) + 4 * h;
+    float m[4][2];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const float m0 = acc[4 * i][r], m1 = acc[4 * i + 1][r], m2 = acc[4 * i + 2][r], m3 = acc[4 * i + 3][r];
+      m[i][0] = m0 + m1 + m2;
+      m[i][1] = m1 - m2 - m3;
+    }
+    const int oy0 = 2 * (by * kT + (tile >> 3)), ox0 = 2 * (bx * kT + (tile & 7));
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      const float e1 = -m[2][q] - m[3][q];
+      float y0 = m[0][q] + m[1][q] + m[2][q] + bias;
+      float y1 = m[1][q] + e1 + bias;
+      if (p.relu) {
+        y0 = fmaxf(y0, 0.f);
+        y1 = fmaxf(y1, 0.f);
+      }
+      const int ox = ox0 + q;
+      if (ox < p.Wo) {
+        const long long i0 = ((long long)(b * p.Ho + oy0) * p.Wo + ox) * p.ldc + co;
+        const long long i1 = i0 + (long long)p.Wo * p.ldc;
+        if (p.mask) {
+          if (oy0 < p.Ho && !(p.mask[i0] > 0.f)) y0 = 0.f;
+          if (oy0 + 1 < p.Ho && !(p.mask[i1] > 0.f)) y1 = 0.f;
+        }
+        if (oy0 < p.Ho) p.y[i0] = y0;
+        if (oy0 + 1 < p.Ho) p.y[i1] = y1;
+      }
+    }
+  }
+}
+
+// U = G g G^T per (co, ci) as in wino_weights_kernel, split into three bf16 planes;
+// w [Cout][3][3][Cin] -> up [Cin/16][16][3][Cout][16]
+__global__ void wino_weights_s3_kernel(const float* __restrict__ w, bf16* __restrict__ up, int Cout, int Cin) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long long)Cout * Cin) return;
+  const int ci = (int)(i % Cin), co = (int)(i / Cin);
+  float g[9];
+#pragma unroll
+  for (int t = 0; t < 9; ++t) g[t] = w[((long long)co * 9 + t) * Cin + ci];
+  float gg[12];  // (G g)[i][kx]
+#pragma unroll
+  for (int kx = 0; kx < 3; ++kx) {
+    const float a = g[kx], bb = g[3 + kx], c = g[6 + kx];
+    gg[0 * 3 + kx] = a;
+    gg[1 * 3 + kx] = 0.5f * (a + bb + c);
+    gg[2 * 3 + kx] = 0.5f * (a - bb + c);
+    gg[3 * 3 + kx] = c;
+  }
+  bf16* ub = up + ((long long)(ci / kSK) * 48 * Cout + co) * kSK + (ci % kSK);
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const float a = gg[3 * r], bb = gg[3 * r + 1], c = gg[3 * r + 2];
+    const float v[4] = {a, 0.5f * (a + bb + c), 0.5f * (a - bb + c), c};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const bf16 p0 = (bf16)v[j];
+      const float r1 = v[j] - (float)p0;
+      const bf16 p1 = (bf16)r1;
+      bf16* o = ub + (long long)(4 * r + j) * 3 * Cout * kSK;
+      o[0] = p0;
+      o[(long long)Cout * kSK] = p1;
+      o[2LL * Cout * kSK] = (bf16)(r1 - (float)p1);
+    }
+  }
+}
+
 // U = G g G^T per (co, ci); w [Cout][3][3][Cin] -> u [Cin/8][16][Cout][8]
 __global__ void wino_weights_kernel(const float* __restrict__ w, float* __restrict__ u, int Cout, int Cin) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -915,9 +1208,10 @@ extern "C" int mhada_wino_weights(const float* w, float* u, int Cout, int Cin, m
   return check_launch("mhada_wino_weights");
 }
 
-extern "C" int mhada_conv3x3_wino(const float* x, const float* u, const float* bias, float* y, int B, int H, int W,
-                                  int Cin, int Cout, long long ldc, int pad_mode, int pad, int relu,
-                                  const float* relu_mask, mhada_stream_t s_) {
+// up: the plane image of mhada_wino_weights_split3, or null (mhada_conv3x3_wino)
+static int conv3x3_wino_launch(const float* x, const float* u, const void* up, const float* bias, float* y, int B,
+                               int H, int W, int Cin, int Cout, long long ldc, int pad_mode, int pad, int relu,
+                               const float* relu_mask, mhada_stream_t s_) {
   if (!x || !u || !y || B <= 0 || H < 2 || W < 2 || Cin <= 0 || Cout <= 0)
     return fail("mhada_conv3x3_wino: bad args");
   if (Cin % kCK || Cout % kCO) return fail("mhada_conv3x3_wino: needs Cin % 8 == 0 and Cout % 64 == 0");
@@ -942,10 +1236,38 @@ extern "C" int mhada_conv3x3_wino(const float* x, const float* u, const float* b
   if (nblk > (1LL << 31) - 1 || (long long)B * H * W * Cin > (1LL << 31) - 1)
     return fail("mhada_conv3x3_wino: problem too large for 32-bit indexing");
   p.nblk = (int)nblk;
-  // the 4-wave form addresses x through a buffer resource: byte size below the out-of-range offset
-  if (tuning().wino4 && (long long)B * H * W * Cin * 4 < 0x7ff00000LL) {
+  // the 4-wave forms address x through a buffer resource: byte size below the out-of-range offset
+  const bool bufx = (long long)B * H * W * Cin * 4 < 0x7ff00000LL;
+  if (up && tuning().wino_split3 && Cin % kSK == 0 && bufx && (long long)Cin * Cout * 96 < 0x7ff00000LL) {
+    if ((uintptr_t)up & 15) return fail("mhada_conv3x3_wino_split3: up must be 16-byte aligned");
+    WinoS3P q;
+    static_cast<WinoP&>(q) = p;
+    q.up = (const bf16*)up;
+    hipLaunchKernelGGL(wino_s3_kernel, dim3(p.nblk), dim3(256), 0, (hipStream_t)s_, q);
+  } else if (tuning().wino4 && bufx) {
     hipLaunchKernelGGL(wino4_kernel<WINO4_DBG>, dim3(p.nblk), dim3(256), 0, (hipStream_t)s_, p);
   } else
     hipLaunchKernelGGL(wino_kernel, dim3(p.nblk), dim3(512), 0, (hipStream_t)s_, p);
   return check_launch("mhada_conv3x3_wino");
+}
+
+extern "C" int mhada_conv3x3_wino(const float* x, const float* u, const float* bias, float* y, int B, int H, int W,
+                                  int Cin, int Cout, long long ldc, int pad_mode, int pad, int relu,
+                                  const float* relu_mask, mhada_stream_t s_) {
+  return conv3x3_wino_launch(x, u, nullptr, bias, y, B, H, W, Cin, Cout, ldc, pad_mode, pad, relu, relu_mask, s_);
+}
+
+extern "C" int mhada_conv3x3_wino_split3(const float* x, const float* u, const void* up, const float* bias, float* y,
+                                         int B, int H, int W, int Cin, int Cout, long long ldc, int pad_mode, int pad,
+                                         int relu, const float* relu_mask, mhada_stream_t s_) {
+  if (!up) return fail("mhada_conv3x3_wino_split3: bad args");
+  return conv3x3_wino_launch(x, u, up, bias, y, B, H, W, Cin, Cout, ldc, pad_mode, pad, relu, relu_mask, s_);
+}
+
+extern "C" int mhada_wino_weights_split3(const float* w, void* up, int Cout, int Cin, mhada_stream_t s_) {
+  if (!w || !up || Cout <= 0 || Cin <= 0 || Cin % kSK) return fail("mhada_wino_weights_split3: bad args (Cin % 16 == 0)");
+  const long long n = (long long)Cout * Cin;
+  hipLaunchKernelGGL(wino_weights_s3_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)s_, w,
+                     (bf16*)up, Cout, Cin);
+  return check_launch("mhada_wino_weights_split3");
 }

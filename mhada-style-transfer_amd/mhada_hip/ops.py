@@ -196,8 +196,24 @@ def conv3x3_wgrad_wino(x: torch.Tensor, g: torch.Tensor, cout: int, pad_mode: st
     return dw, db
 
 
+def wino_weights_split3(w: torch.Tensor) -> torch.Tensor:
+    """``mhada_wino_weights_split3``: w packed [Cout][9*Cin] fp32 (Cin % 16 == 0) -> the three
+    round-to-nearest bf16 planes of U, [Cin/16][16][3][Cout][16] (p0 + p1 + p2 = the U of
+    ``wino_weights``)."""
+    _need_gpu(w)
+    Co, K = w.shape
+    Ci = K // 9
+    if w.dtype != torch.float32 or K != 9 * Ci or Ci % 16 or not w.is_contiguous():
+        raise ValueError("wino_weights_split3 needs a contiguous fp32 [Cout][9*Cin] weight, Cin % 16 == 0")
+    up = torch.empty(Ci // 16, 16, 3, Co, 16, device=w.device, dtype=torch.bfloat16)
+    _call("mhada_wino_weights_split3", w, w.data_ptr(), up.data_ptr(), Co, Ci)
+    return up
+
+
 def wino_weights(w: torch.Tensor) -> torch.Tensor:
-    """``mhada_wino_weights``: w packed [Cout][9*Cin] fp32 -> U [Cin/8][16][Cout][8]."""
+    """``mhada_wino_weights``: w packed [Cout][9*Cin] fp32 -> U [Cin/8][16][Cout][8].  For
+    Cin % 16 == 0 the result also carries the plane image of ``wino_weights_split3`` (attribute
+    ``split3``), which ``conv3x3_wino`` hands to the SPLIT3 kernel."""
     _need_gpu(w)
     Co, K = w.shape
     Ci = K // 9
@@ -205,14 +221,17 @@ def wino_weights(w: torch.Tensor) -> torch.Tensor:
         raise ValueError("wino_weights needs a contiguous fp32 [Cout][9*Cin] weight")
     u = torch.empty(Ci // 8, 16, Co, 8, device=w.device, dtype=torch.float32)
     _call("mhada_wino_weights", w, w.data_ptr(), u.data_ptr(), Co, Ci)
+    if Ci % 16 == 0:
+        u.split3 = wino_weights_split3(w)
     return u
 
 
 def conv3x3_wino(x: torch.Tensor, u: torch.Tensor, bias: Optional[torch.Tensor], relu: bool = True,
                  pad_mode: str = "reflect", pad: int = 1, out: Optional[torch.Tensor] = None,
                  relu_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """``mhada_conv3x3_wino``: fp32 NHWC conv3x3 from the transformed filters ``u``; ``relu_mask``
-    (the output's layout): zero the outputs where relu_mask <= 0 (a folded ReLU adjoint)."""
+    """``mhada_conv3x3_wino`` / ``mhada_conv3x3_wino_split3``: fp32 NHWC conv3x3 from the
+    transformed filters ``u`` of ``wino_weights``; ``relu_mask`` (the output's layout): zero the
+    outputs where relu_mask <= 0 (a folded ReLU adjoint)."""
     _need_gpu(x, u, bias, out, relu_mask)
     B, H, W, Ci = x.shape
     Co = u.shape[2]
@@ -230,8 +249,13 @@ def conv3x3_wino(x: torch.Tensor, u: torch.Tensor, bias: Optional[torch.Tensor],
     if relu_mask is not None and (relu_mask.shape != y.shape or relu_mask.dtype != torch.float32
                                   or not relu_mask.is_contiguous()):
         raise ValueError("conv3x3_wino: relu_mask must be a contiguous fp32 tensor shaped like the output")
-    _call("mhada_conv3x3_wino", x, x.data_ptr(), u.data_ptr(), _ptr(bias), y.data_ptr(), B, H, W, Ci, Co,
-          y.shape[-1], mode, pad, int(relu), _ptr(relu_mask))
+    up = getattr(u, "split3", None)
+    if up is not None:  # the library takes the SPLIT3 kernel (tuning wino_split3) or falls back to u
+        _call("mhada_conv3x3_wino_split3", x, x.data_ptr(), u.data_ptr(), up.data_ptr(), _ptr(bias), y.data_ptr(),
+              B, H, W, Ci, Co, y.shape[-1], mode, pad, int(relu), _ptr(relu_mask))
+    else:
+        _call("mhada_conv3x3_wino", x, x.data_ptr(), u.data_ptr(), _ptr(bias), y.data_ptr(), B, H, W, Ci, Co,
+              y.shape[-1], mode, pad, int(relu), _ptr(relu_mask))
     return y
 
 
