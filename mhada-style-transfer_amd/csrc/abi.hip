@@ -40,7 +40,7 @@ const Knob kKnobs[] = {
     {"gemm_ldsepi", &Tuning::gemm_ldsepi},           {"gemm_n64", &Tuning::gemm_n64},
     {"conv_c64", &Tuning::conv_c64},                 {"conv_dir", &Tuning::conv_dir},                 {"gemm_rinit", &Tuning::gemm_rinit},
     {"tn_skinny_lds", &Tuning::tn_skinny_lds},       {"train_dkv_dma", &Tuning::train_dkv_dma},
-    {"wino_split3", &Tuning::wino_split3},
+    {"wino_split3", &Tuning::wino_split3},           {"gemm_s3_order", &Tuning::gemm_s3_order},
     {"wino4", &Tuning::wino4},                       {"upsample_quad", &Tuning::upsample_quad},
     {"xknob", &Tuning::xknob},
 };

@@ -123,14 +123,21 @@ MHADA_DEV bool conv_src(const GemmP& p, int y, int x, int dy, int dx, int& Y, in
 // the plain ROWS path stages raw chunks with no per-element work.
 constexpr int kRowsCentred = 100;
 // MHADA_A_SPLIT3 (fp32-accurate products on the bf16 MFMA): A is three bf16 planes p0 + p1 + p2 of
-// an fp32 matrix (8 + 8 + 8 mantissa bits), the GEMM's K = 6 K0 is virtual: K-tile 6 kk + t reads
-// columns 64 kk .. of plane kSplitPlanes[t] = 1, 2, 0, 1, 0, 0, and W holds the matching [N][6 K0]
-// interleave (chunk kk of q1, q0, q2, q0, q1, q0), so the fp32 accumulators sum p1 q1 + p2 q0 +
-// p0 q2 + p1 q0 + p0 q1 + p0 q0 chunk by chunk: every cross product p_i q_j with i + j <= 2.  With
-// round-to-nearest planes |p1| <= 2^-8 |x|, |p2| <= 2^-16 |x| (likewise q), so the three dropped
-// terms are below 2^-24 |x w| (p1 q2 and p2 q1) and 2^-32 |x w| (p2 q2) per product.
+// an fp32 matrix (8 + 8 + 8 mantissa bits), the GEMM's K = 6 K0 is virtual, and W holds the [N][6 K0]
+// interleave (per 64-column chunk kk the blocks q1, q0, q2, q0, q1, q0).  Per chunk the fp32
+// accumulators take every cross product p_i q_j with i + j <= 2; the order inside a chunk carries no
+// accuracy (after the first chunk, or a preloaded residual, the accumulator already holds
+// full-magnitude terms).  Default (tuning gemm_s3_order = 1, gemm_s3_kernel):
+//     p2 q0 -> p1 q0 -> p1 q1 -> p0 q1 -> p0 q2 -> p0 q0
+// consecutive terms share one operand, A and W have their own LDS rings and each plane is staged
+// once per chunk (q0 twice): 7 stagings of 32 KiB, W read from blocks 1, 0, 2 of the interleave only.
+// gemm_s3_order = 0 (gemm_ppp_kernel<bf16, TO, kRowsSplit3>): K-tile 6 kk + t is an ordinary K-tile
+// that stages plane kSplitPlanes[t] = 1, 2, 0, 1, 0, 0 of A and block t of W, i.e. p1 q1 + p2 q0 +
+// p0 q2 + p1 q0 + p0 q1 + p0 q0 with 12 stagings per chunk.  With round-to-nearest planes
+// |p1| <= 2^-8 |x|, |p2| <= 2^-16 |x| (likewise q), so the three dropped terms are below 2^-24 |x w|
+// (p1 q2 and p2 q1) and 2^-32 |x w| (p2 q2) per product.
 constexpr int kRowsSplit3 = 101;
-constexpr int kSplitPlanes = 0x001021;  // nibble t = plane of K-block t
+constexpr int kSplitPlanes = 0x001021;  // nibble t = plane of K-block t (gemm_s3_order = 0)
 
 // ------------------------------------------------------------------------------------
 // A-operand staging for one K step.  Each thread owns A_CH chunks: rows (tid>>3)+32*i,
@@ -1222,6 +1229,250 @@ __global__ void __launch_bounds__(512) gemm_ppp_kernel(const GemmP p, int total)
 }
 
 // ------------------------------------------------------------------------------------
+// SPLIT3 form of the persistent ping-pong kernel that stages every operand plane ONCE per
+// 64-column chunk (tuning gemm_s3_order = 1, the default; 0: gemm_ppp_kernel<bf16, TO, kRowsSplit3>,
+// which walks the chunk as six ordinary K-tiles and stages both operands for each: twelve 32-KiB
+// stagings for six distinct blocks).  Same 256x256 tile, wave layout, phases, swizzle, accumulator
+// init (rinit), epilogues (plane output included) and xcd_remap as gemm_ppp_kernel; what differs:
+//   * the six terms run in the order kS3Terms, where consecutive K-tiles differ in ONE operand;
+//   * A and W have their own 2-slot LDS rings (2 x 32 KiB each + the 32 KiB epilogue scratch =
+//     160 KiB), each advanced only when its operand changes: 7 stagings per chunk, A three times
+//     (p2, p1, p0), W four (q0, q1, q2 and q0 again for the last term; a slot is overwritten two
+//     stagings later, so q0 cannot be kept across q1 and q2);
+//   * W is read from the [N][6 K0] interleave's blocks 1 (q0), 0 (q1) and 2 (q2) of each 6-block
+//     chunk; blocks 3-5 (the copies) are not touched.
+// Per chunk c (A slot a = c & 1, flipped every chunk since 3 A stagings; W slots are static):
+//   t  term     reads A/W slot  phases 0,1 stage W       phase 3 stages A       may stay in flight
+//   0  p2 q0    a    / 0        q1(c)   -> W slot 1      p0(c)   -> A slot a    q1, p0 (8 pieces)
+//   1  p1 q0    a^1  / 0        -                        -                      p0 (4)
+//   2  p1 q1    a^1  / 1        q2(c)   -> W slot 0      p2(c+1) -> A slot a^1  q2, p2' (8)
+//   3  p0 q1    a    / 1        -                        -                      p2' (4)
+//   4  p0 q2    a    / 0        q0(c)   -> W slot 1      -                      none
+//   5  p0 q0    a    / 1        q0(c+1) -> W slot 0      p1(c+1) -> A slot a    p1' (4)
+// A slot is refilled in phase 3 of the last K-tile that reads it (after both groups' phase-2 reads,
+// as in gemm_ppp_kernel) and a W slot in phases 0/1 of the K-tile after its last read.  vmcnt
+// retires in order, so each K-tile's wait is "everything but the newest n pieces": every operand
+// has landed one whole K-tile before the barrier that publishes it except q0 (twice) and p1', which
+// have the one K-tile of lead that gemm_ppp_kernel gives all of A.  Chunk c + 1 may be the next
+// output tile's first chunk: the stream runs on across tiles, and the first wait of a tile may leave
+// the previous tile's epilogue stores in flight (p1' is older than them, q1 and p0 younger).
+// Registers (hipcc, ROCm 7): 256 VGPRs with 6 spilled.  The six values (column indices of zero_acc's
+// residual loads) are written to scratch once in the kernel prologue, before the first MFMA, and read back only in
+// the rinit residual loads of zero_acc at a tile boundary: the K loop holds no scratch access, so
+// the counted waits there see the DMA pieces and the epilogue's stores alone.
+// ------------------------------------------------------------------------------------
+template <typename TO>
+__global__ void __launch_bounds__(512) gemm_s3_kernel(const GemmP p, int total) {
+  constexpr int BK = 64, PE = 512, HALF = 128 * BK, SLOT = 2 * HALF;  // bf16 elements
+  constexpr int SCR = 8 * 4096 / 2;
+  __shared__ __attribute__((aligned(16))) bf16 smem[4 * SLOT + SCR];  // 160 KiB, the only LDS object
+  bf16* const smA = smem;
+  bf16* const smW = smem + 2 * SLOT;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int grp = wave >> 2, wc = wave & 3;
+  const int h = lane >> 5, r32 = lane & 31;
+  const int G = gridDim.x;
+
+  int cofs[2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i) cofs[i] = 8 * ((lane & 7) ^ (4 * i + (lane >> 4)));
+  // per-tile staging state (rows 16*wave + 8i + (lane>>3) of each 128-row half); one problem (nz = 1)
+  struct St {
+    unsigned aoff[2][2], woff[2][2];
+    int m0, n0;
+  };
+  const bf16* const ab = reinterpret_cast<const bf16*>(p.a);
+  const bf16* const wb = reinterpret_cast<const bf16*>(p.w);
+  auto setup = [&](int w, St& s) {
+    const int t = xcd_remap(w, total);
+    const int tm = t / p.tiles_n, tn = t - tm * p.tiles_n;
+    s.m0 = tm * 256;
+    s.n0 = tn * 256;
+#pragma unroll
+    for (int hh = 0; hh < 2; ++hh)
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        const int rr = 16 * wave + 8 * i + (lane >> 3);
+        const int m = min(s.m0 + 128 * hh + rr, p.M - 1);
+        const int n = min(s.n0 + 128 * hh + rr, p.N - 1);
+        s.woff[hh][i] = (unsigned)((long long)n * p.ldw + cofs[i]);
+        s.aoff[hh][i] = (unsigned)((long long)m * p.lda + cofs[i]);
+      }
+  };
+  // plane `pl` of A, columns 64 kk .. 64 kk + 63, both row halves (4 pieces per wave)
+  auto stage_a = [&](const St& s, int pl, int kk, int slot) {
+    const bf16* src = ab + pl * p.spl + kk * BK;
+    bf16* dst = smA + slot * SLOT + wave * 2 * PE;
+#pragma unroll
+    for (int hh = 0; hh < 2; ++hh)
+#pragma unroll
+      for (int i = 0; i < 2; ++i) glds16(src + s.aoff[hh][i], dst + hh * HALF + PE * i);
+  };
+  // block `blk` (0: q1, 1: q0, 2: q2) of chunk kk of the weight interleave, row half hh (2 pieces)
+  auto stage_w = [&](const St& s, int hh, int blk, int kk, int slot) {
+    const bf16* src = wb + (6 * kk + blk) * BK;
+    bf16* dst = smW + slot * SLOT + hh * HALF + wave * 2 * PE;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) glds16(src + s.woff[hh][i], dst + PE * i);
+  };
+
+  // fragment reads as gemm_ppp_kernel (bf16): k-step ks takes chunk 2ks + h at slot (2ks + h) ^ swz
+  const int swz = (r32 >> 1) & 7;
+  int koff[4];
+#pragma unroll
+  for (int ks = 0; ks < 4; ++ks) koff[ks] = 8 * ((2 * ks + h) ^ swz);
+  const bf16* sA = smA + grp * HALF + r32 * BK;
+  const bf16* sW = smW + (wc >> 1) * HALF + ((wc & 1) * 64 + r32) * BK;
+  bf16x8 af[4][2], wf[2][2];
+  auto read_a = [&](int kp, int slot) {
+#pragma unroll
+    for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+      for (int s2 = 0; s2 < 2; ++s2)
+        af[mt][s2] = *reinterpret_cast<const bf16x8*>(sA + slot * SLOT + mt * 32 * BK + koff[2 * kp + s2]);
+  };
+  auto read_w = [&](int nt, int kp, int slot) {
+#pragma unroll
+    for (int s2 = 0; s2 < 2; ++s2)
+      wf[nt][s2] = *reinterpret_cast<const bf16x8*>(sW + slot * SLOT + nt * 32 * BK + koff[2 * kp + s2]);
+  };
+  f32x16 acc[4][2];
+  // zero, or (p.rinit) the tile's residual rows + bias: see gemm_ppp_kernel
+  auto zero_acc = [&](const St& s) {
+    if constexpr (sizeof(TO) == 4) {
+      if (p.rinit) {
+        const float* rb = reinterpret_cast<const float*>(p.r);
+        const float* bb = p.bias;
+#pragma unroll
+        for (int nt = 0; nt < 2; ++nt)
+#pragma unroll
+          for (int g = 0; g < 4; ++g) {
+            const int n = s.n0 + wc * 64 + nt * 32 + 8 * g + 4 * h;
+            const bool nok = n + 3 < p.N;
+            const f32x4 b4 = (bb && nok) ? *reinterpret_cast<const f32x4*>(bb + n) : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int mt = 0; mt < 4; ++mt) {
+              const int m = s.m0 + grp * 128 + mt * 32 + r32;
+              f32x4 r4 = {0.f, 0.f, 0.f, 0.f};
+              if (nok && m < p.M) r4 = *reinterpret_cast<const f32x4*>(rb + (long long)m * p.ldr + n);
+#pragma unroll
+              for (int e = 0; e < 4; ++e) acc[mt][nt][4 * g + e] = r4[e] + b4[e];
+            }
+          }
+        return;
+      }
+    }
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+#pragma unroll
+      for (int b = 0; b < 2; ++b)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc[a][b][e] = 0.f;
+  };
+  GemmP pe = p;
+  if (p.rinit) {
+    pe.r = nullptr;
+    pe.bias = nullptr;
+  }
+  auto compute = [&](int nt) {
+    __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+    for (int s2 = 0; s2 < 2; ++s2)
+#pragma unroll
+      for (int mt = 0; mt < 4; ++mt)
+        acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[nt][s2], af[mt][s2], acc[mt][nt], 0, 0, 0);
+    __builtin_amdgcn_s_setprio(0);
+  };
+  // a full tile's epilogue issues at least this many stores per wave
+  constexpr int EPI_MIN = sizeof(TO) == 4 ? 32 : 16;
+  auto wait_vm = [&](int keep) __attribute__((always_inline)) {
+    if (keep == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    else if (keep == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+    else if (keep == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+    else asm volatile("s_waitcnt vmcnt(%0)" :: "n"(8 + EPI_MIN) : "memory");
+  };
+  // one K-tile on A slot as / W slot ws.  sw: stage W block wblk of chunk wkk of tile wt into W slot
+  // wsl (phases 0 and 1); sa: stage A plane apl of chunk akk of tile at into A slot asl (phase 3);
+  // keep: the wave's newest pieces that may stay in flight past this K-tile.
+  auto ktile = [&](int as, int ws, bool sw, const St& wt, int wblk, int wkk, int wsl, bool sa, const St& at, int apl,
+                   int akk, int asl, int keep) __attribute__((always_inline)) {
+    // phase 0
+    read_a(0, as); read_w(0, 0, ws);
+    if (sw) stage_w(wt, 0, wblk, wkk, wsl);
+    PP_LGKM0(); PP_BARRIER(); compute(0); PP_BARRIER();
+    // phase 1
+    read_w(1, 0, ws);
+    if (sw) stage_w(wt, 1, wblk, wkk, wsl);
+    PP_LGKM0(); PP_BARRIER(); compute(1); PP_BARRIER();
+    // phase 2
+    read_a(1, as); read_w(0, 1, ws);
+    PP_LGKM0(); PP_BARRIER(); compute(0); PP_BARRIER();
+    // phase 3
+    read_w(1, 1, ws);
+    if (sa) stage_a(at, apl, akk, asl);
+    wait_vm(keep);
+    PP_LGKM0(); PP_BARRIER(); compute(1); PP_BARRIER();
+  };
+  int ap = 0;  // A slot of this chunk's p2 and p0 (p1: ap ^ 1)
+  // chunk kk of tile sc; the lookahead reaches chunk kn of tile sn (nx: there is one).  The two call
+  // sites bind sn to `cur` or `nxt` at compile time (a runtime choice made hipcc copy the state).
+  // wx: the tile's first wait may leave EPI_MIN stores of the previous epilogue in flight.
+  auto chunk = [&](const St& sc, int kk, const St& sn, int kn, bool nx, bool wx) __attribute__((always_inline)) {
+    const int a0 = ap, a1 = ap ^ 1;
+    ktile(a0, 0, true, sc, 0, kk, 1, true, sc, 0, kk, a0, wx ? 8 + EPI_MIN : 8);  // p2 q0
+    ktile(a1, 0, false, sc, 0, 0, 0, false, sc, 0, 0, 0, 4);                      // p1 q0
+    ktile(a1, 1, true, sc, 2, kk, 0, nx, sn, 2, kn, a1, nx ? 8 : 4);              // p1 q1
+    ktile(a0, 1, false, sc, 0, 0, 0, false, sc, 0, 0, 0, nx ? 4 : 0);             // p0 q1
+    ktile(a0, 0, true, sc, 1, kk, 1, false, sc, 0, 0, 0, 0);                      // p0 q2
+    ktile(a0, 1, nx, sn, 1, kn, 0, nx, sn, 1, kn, a0, nx ? 4 : 0);                // p0 q0
+    ap ^= 1;
+  };
+
+  const int KC = p.K / (6 * BK);
+  int w = blockIdx.x;
+  St cur, nxt;
+  setup(w, cur);
+  bool has_nxt = w + G < total;
+  if (has_nxt) setup(w + G, nxt);
+  zero_acc(cur);
+  stage_a(cur, 2, 0, 0);
+  stage_w(cur, 0, 1, 0, 0); stage_w(cur, 1, 1, 0, 0);
+  stage_a(cur, 1, 0, 1);
+  asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+  PP_BARRIER();
+  if (grp == 1) PP_BARRIER();  // group 1 runs one barrier behind
+
+  bool lazy = false;  // the previous tile's epilogue stores may still be in flight
+  while (true) {
+    for (int kk = 0; kk + 1 < KC; ++kk) chunk(cur, kk, cur, kk + 1, true, kk == 0 && lazy);
+    chunk(cur, KC - 1, nxt, 0, has_nxt, KC == 1 && lazy);
+    // tile boundary: re-align the groups so both store in the same interval, then re-stagger
+    if (grp == 0) PP_BARRIER();
+    // a full tile's stores need not drain before the next tile's first wait (not with rinit: the
+    // residual loads follow the stores and the first MFMA needs them)
+    lazy = has_nxt && !p.rinit && cur.m0 + 256 <= p.M && cur.n0 + 256 <= p.N;
+    __builtin_amdgcn_sched_barrier(0);
+    if (p.lds_epi) {
+      float* scr = reinterpret_cast<float*>(smem + 4 * SLOT) + wave * 1024;
+      if constexpr (sizeof(TO) == 2)
+        store_tile_lds_bf16<4>(pe, acc, 0, 0, cur.m0 + grp * 128, cur.n0 + wc * 64, lane, scr);
+      else
+        store_tile_lds<TO, 4, 2, true>(pe, acc, 0, 0, cur.m0 + grp * 128, cur.n0 + wc * 64, lane, scr);
+    } else {
+      store_tile<TO, 4, 2>(pe, acc, 0, 0, cur.m0 + grp * 128 + r32, cur.n0 + wc * 64, h);
+    }
+    if (!has_nxt) break;
+    if (grp == 1) PP_BARRIER();
+    zero_acc(nxt);
+    cur = nxt;
+    w += G;
+    has_nxt = w + G < total;
+    if (has_nxt) setup(w + G, nxt);
+  }
+}
+
+// ------------------------------------------------------------------------------------
 // fp32 GEMM for N <= 64 columns over long K (the attention backward's dQ = dS K: M = Nc, K = Ns,
 // one problem per (batch, head); the grouped per-head 1x1 convs).  Streaming A is the whole
 // cost: at the fp32 MFMA rate a 128x64 tile consumes 8 B/clk/CU of A, ~5 TB/s chip-wide, so the
@@ -1350,6 +1601,14 @@ static int launch_gemm_pp(const GemmP& p0, int nz, hipStream_t stream) {
   p.rinit = (sizeof(TO) == 4 && p.r && !p.relu && tuning().gemm_rinit && ((uintptr_t)p.r & 15) == 0 &&
              p.ldr % 4 == 0 && p.sr1 % 4 == 0 && p.sr2 % 4 == 0 && p.N % 4 == 0) ? 1 : 0;
   const long long total = (long long)p.ntiles * nz;
+  if constexpr (AMODE == kRowsSplit3 && sizeof(TC) == 2 && BN == 256) {
+    // each operand plane staged once per chunk (tuning gemm_s3_order = 0: the six-K-tile walk below)
+    if (tuning().gemm_s3_order && nz == 1 && total < (1LL << 31)) {
+      const int grid = (int)std::min<long long>(total, num_cus());
+      hipLaunchKernelGGL((gemm_s3_kernel<TO>), dim3(grid), dim3(512), 0, stream, p, (int)total);
+      return check_launch("mhada_gemm");
+    }
+  }
   if (sizeof(TC) == 4 || BN != 256 || AMODE == kRowsSplit3 || (p.K >= 128 && persist_enabled() && total < (1LL << 31))) {
     const int grid = (int)std::min<long long>(total, num_cus());
     hipLaunchKernelGGL((gemm_ppp_kernel<TC, TO, AMODE, BN>), dim3(grid), dim3(512), 0, stream, p, (int)total);
