@@ -729,6 +729,18 @@ __global__ void __launch_bounds__(64 * WM * WN) gemm_kernel(const GemmP p) {
     if constexpr (TN == 2) {
       store_vt_tile<TO, TM>(p, acc, z1, z2, m0 + wm * (BM / WM), n0 + wn * (BN / WN), lane,
                             reinterpret_cast<float*>(smem) + wave * 1024);
+      // an ldt beyond the last row tile's BM positions: the rest of each image row is zero too
+      if (wm == 0 && m0 + BM >= p.M && m0 + BM < p.ldt) {
+        constexpr int EV = 16 / (int)sizeof(TO);
+        TO* vbase = reinterpret_cast<TO*>(p.vt) + z1 * p.svt1 + z2 * p.svt2;
+        const int cov = m0 + BM, per_row = ((int)p.ldt - cov) / EV;  // ldt % 64 == 0, BM % 64 == 0
+        typename Vec16<TO>::type zv;
+#pragma unroll
+        for (int e = 0; e < EV; ++e) zv[e] = (TO)0.0f;
+        for (int i = lane; i < 128 * per_row; i += 64)
+          *reinterpret_cast<typename Vec16<TO>::type*>(vbase + (long long)(i / per_row) * p.ldt + cov +
+                                                      (i % per_row) * EV) = zv;
+      }
     }
     return;
   }
@@ -1206,8 +1218,13 @@ __global__ void __launch_bounds__(512) gemm_ppp_kernel(const GemmP p, int total)
     if constexpr (SCR > 0) {
       if (p.lds_epi) {
         float* scr = reinterpret_cast<float*>(smem + NSLOT * TILE) + wave * 1024;
+        // (the 16-B bf16 form has no residual add: a bf16 residual takes the 8-B form, as in gemm_kernel)
         if constexpr (sizeof(TO) == 2 && TN == 2) {
-          store_tile_lds_bf16<4>(pe, acc, cur.z1, cur.z2, cur.m0 + grp * 128, cur.n0 + wc * TN * 32, lane, scr);
+          if (!pe.r)
+            store_tile_lds_bf16<4>(pe, acc, cur.z1, cur.z2, cur.m0 + grp * 128, cur.n0 + wc * TN * 32, lane, scr);
+          else
+            store_tile_lds<TO, 4, TN, AMODE == kRowsSplit3>(pe, acc, cur.z1, cur.z2, cur.m0 + grp * 128,
+                                                             cur.n0 + wc * TN * 32, lane, scr);
         } else {
           store_tile_lds<TO, 4, TN, AMODE == kRowsSplit3>(pe, acc, cur.z1, cur.z2, cur.m0 + grp * 128,
                                                            cur.n0 + wc * TN * 32, lane, scr);
@@ -1455,10 +1472,12 @@ __global__ void __launch_bounds__(512) gemm_s3_kernel(const GemmP p, int total) 
     __builtin_amdgcn_sched_barrier(0);
     if (p.lds_epi) {
       float* scr = reinterpret_cast<float*>(smem + 4 * SLOT) + wave * 1024;
-      if constexpr (sizeof(TO) == 2)
-        store_tile_lds_bf16<4>(pe, acc, 0, 0, cur.m0 + grp * 128, cur.n0 + wc * 64, lane, scr);
-      else
-        store_tile_lds<TO, 4, 2, true>(pe, acc, 0, 0, cur.m0 + grp * 128, cur.n0 + wc * 64, lane, scr);
+      bool wide = false;  // (a bf16 residual takes the 8-B form: see gemm_ppp_kernel)
+      if constexpr (sizeof(TO) == 2) {
+        wide = !pe.r;
+        if (wide) store_tile_lds_bf16<4>(pe, acc, 0, 0, cur.m0 + grp * 128, cur.n0 + wc * 64, lane, scr);
+      }
+      if (!wide) store_tile_lds<TO, 4, 2, true>(pe, acc, 0, 0, cur.m0 + grp * 128, cur.n0 + wc * 64, lane, scr);
     } else {
       store_tile<TO, 4, 2>(pe, acc, 0, 0, cur.m0 + grp * 128 + r32, cur.n0 + wc * 64, h);
     }
