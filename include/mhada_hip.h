@@ -51,7 +51,7 @@ enum {
  * p0 = bf16(y), p1 = bf16(y - p0), p2 = bf16(y - p0 - p1) of the fp32 result y (ABI 15) */
 enum { MHADA_BF16X3 = 2 };
 
-int mhada_abi_version(void);  /* 17 (mhada_wino_weights_split3 / mhada_conv3x3_wino_split3, knob wino_split3; 16: mhada_split3_kv / mhada_attn_split3; 15: mhada_gemm a_mode MHADA_A_SPLIT3, mhada_layernorm y_dtype MHADA_BF16X3; 14: mhada_cosine_moments / mhada_cosine_attn, mhada_warp_bwd; 13: mhada_clock_probe; tuning knobs of removed kernel variants dropped, attn_waves 0 = auto; 12: mhada_feat_stats; 11: mhada_transpose64; 10: mhada_attn_train_fwd_vt; 9: 3-channel conv adjoints mhada_vgg_stem_dgrad / mhada_out3_dgrad / mhada_out3_wgrad; 8: mhada_feat_loss_bwd; 7: gemm c2 / vt outputs, instnorm / attention backward helpers; 6: LayerNorm / pos-embed training adjoints; 5: Winograd conv; 4: training CONV3X3_ZERO, mhada_gemm_tn, backward helpers) */
+int mhada_abi_version(void);  /* 18 (mhada_fold_block_hd / mhada_cosine_prep_hd / mhada_attn_hd, mhada_vit_batch_attn head_dim 32 | 128; 17: mhada_wino_weights_split3 / mhada_conv3x3_wino_split3, knob wino_split3; 16: mhada_split3_kv / mhada_attn_split3; 15: mhada_gemm a_mode MHADA_A_SPLIT3, mhada_layernorm y_dtype MHADA_BF16X3; 14: mhada_cosine_moments / mhada_cosine_attn, mhada_warp_bwd; 13: mhada_clock_probe; tuning knobs of removed kernel variants dropped, attn_waves 0 = auto; 12: mhada_feat_stats; 11: mhada_transpose64; 10: mhada_attn_train_fwd_vt; 9: 3-channel conv adjoints mhada_vgg_stem_dgrad / mhada_out3_dgrad / mhada_out3_wgrad; 8: mhada_feat_loss_bwd; 7: gemm c2 / vt outputs, instnorm / attention backward helpers; 6: LayerNorm / pos-embed training adjoints; 5: Winograd conv; 4: training CONV3X3_ZERO, mhada_gemm_tn, backward helpers) */
 const char* mhada_last_error(void);
 
 /* Kernel-variant table.  Defaults are the measured winners; the other variants serve A/B
@@ -140,7 +140,9 @@ int mhada_layernorm(const float* x, void* y, int y_dtype, const float* gamma, co
 /* nn.MultiheadAttention(batch_first=False) applied to a (B, N, C) tensor (vit.py:48,59):
  * the SEQUENCE axis is the batch axis.  For each token n and head h:
  *   out[i][n][h] = sum_j softmax_j(q[i][n][h] . k[j][n][h] / sqrt(d)) v[j][n][h]
- * qkv [L][ntok][3C] (packed q|k|v, dtype), out [L][ntok][C] (dtype); L = batch size. */
+ * qkv [L][ntok][3C] (packed q|k|v, dtype), out [L][ntok][C] (dtype); L = batch size.
+ * head_dim d = 64, or (ABI 18; csrc/attn_hd.hip, one kernel for every L) 32 | 128; any other
+ * width returns MHADA_ERR_ARG. */
 int mhada_vit_batch_attn(const void* qkv, void* out, int dtype, int L, int ntok, int heads,
                          int head_dim, mhada_stream_t stream);
 
@@ -192,6 +194,42 @@ int mhada_cosine_prep(void* q, void* kv, int dtype, int B, int H, int Nc, int Ns
 int mhada_attn(const void* q, const void* kv, const void* vt, const float* fcs,
                const float* fcs_mu, const float* fcs_rstd, const float* v_mu, void* out,
                int dtype, int B, int H, int Nc, int Ns, int activation, mhada_stream_t stream);
+
+/* ---- head widths D = 32 | 128 (ABI 18; csrc/attn_hd.hip) ------------------------------------
+ * AdaAttnMultiHead accepts any num_heads dividing qkv_dim (adaDecoder.py:120-145); at 512 channels
+ * 16 and 4 heads give D = 32 and 128.  The three entries below are the D-wide forms of
+ * mhada_fold_block, mhada_cosine_prep and mhada_attn; the 64-wide entries keep their kernels.
+ * All three check their arguments on the host before any launch: D outside {32, 128}, a null
+ * pointer or a non-positive size return MHADA_ERR_ARG with a mhada_last_error text.
+ *
+ * mhada_fold_block_hd (adaDecoder.py:173,178,182): mhada_fold_block's four formulas with 64 -> D:
+ *   wq[b][h][o][c]  = Wf[h][o][c] * rstd_c[b][D h+c]
+ *   wkv[b][h][o][c] = o<D ? Wg[h][o][c] * rstd_s[b][D h+c] * kscale : Wh[h][o-D][c]
+ *   bkv[h][o]       = o<D ? bg[h][o] * kscale : 0
+ *   v_mu[b][D h+o]  = sum_c Wh[h][o][c] * mu_s[b][D h+c] + bh[h][o]
+ * W* fp32 [H][D][D], b* fp32 [H][D], stats fp32 [B][D H]; wq [B][H][D][D], wkv [B][H][2D][D] of
+ * `dtype`, bkv fp32 [H][2D], v_mu fp32 [B][D H]. */
+int mhada_fold_block_hd(const float* wf, const float* wg, const float* wh, const float* bg,
+                        const float* bh, const float* rstd_c, const float* mu_s,
+                        const float* rstd_s, void* wq, void* wkv, float* bkv, float* v_mu,
+                        float kscale, int dtype, int B, int H, int D, mhada_stream_t stream);
+
+/* L2-normalise the D-wide rows of q [B][H][Nc][D] and the K half of kv [B][H][Ns][2D] in place
+ * (CosineSimilarity, adaDecoder.py:30-32).  Nc == 0 (q may be NULL) or Ns == 0 (kv may be NULL)
+ * normalises one side only, as mhada_cosine_prep. */
+int mhada_cosine_prep_hd(void* q, void* kv, int dtype, int B, int H, int D, int Nc, int Ns,
+                         mhada_stream_t stream);
+
+/* The fused MHAda attention (adaDecoder.py:186-198; cosine: adaDecoder.py:20-34 after
+ * mhada_cosine_prep_hd) at D = 32 | 128: mhada_attn's formula and K contract (softmax: the K half
+ * carries log2(e)), the flash loop for both activations (the linear cosine form stays 64-only).
+ * q [B][H][Nc][D], kv [B][H][Ns][2D] (K | V'; read directly, no transposed image), fcs
+ * [B][Nc][D H] fp32 with fcs_mu / fcs_rstd / v_mu [B][D H] fp32; out [B][Nc][D H] of `dtype`.
+ * All pointers 16-byte aligned.  fp32: the exact fp32 MFMA; bf16: bf16 MFMA, fp32 accumulation
+ * and softmax.  Bit-identical from run to run. */
+int mhada_attn_hd(const void* q, const void* kv, const float* fcs, const float* fcs_mu,
+                  const float* fcs_rstd, const float* v_mu, void* out, int dtype, int B, int H,
+                  int D, int Nc, int Ns, int activation, mhada_stream_t stream);
 
 /* The fp32 softmax MHAda attention (adaDecoder.py:186-198, mhada_attn's contract and output) as
  * fp32-accurate SPLIT3 products on the bf16 MFMA (ABI 16; csrc/attn_split3.hip): every fp32 operand as

@@ -61,6 +61,10 @@ int conv3x3_c64(const void* x, const void* w, const float* bias, void* y, int B,
 int conv3x3_dir(const void* x, const void* w, const float* bias, void* y, int B, int H, int W, int cin, int cout,
                 int relu, hipStream_t s);
 
+// attn_hd.hip: the ViT's batch-axis attention at head_dim 32 / 128 (one kernel templated on the width, any
+// L).  Dispatched from mhada_vit_batch_attn.
+int vit_batch_attn_hd(const void* qkv, void* out, int dtype, int L, int ntok, int heads, int head_dim, hipStream_t s);
+
 // ---- scalar conversions -----------------------------------------------------------------
 template <typename T> MHADA_DEV float to_f32(T x);
 template <> MHADA_DEV float to_f32<float>(float x) { return x; }

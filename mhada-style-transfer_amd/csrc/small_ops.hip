@@ -873,7 +873,8 @@ extern "C" int mhada_vit_batch_attn(const void* qkv, void* out, int dtype, int L
                                     int head_dim, mhada_stream_t s_) {
   hipStream_t s = (hipStream_t)s_;
   if (!qkv || !out || L <= 0 || ntok < 0 || heads <= 0) return fail("mhada_vit_batch_attn: bad args");
-  if (head_dim != 64) return fail("mhada_vit_batch_attn: head_dim must be 64");
+  if (head_dim != 64 && head_dim != 32 && head_dim != 128)
+    return fail("mhada_vit_batch_attn: head_dim must be 32, 64 or 128");
   if (ntok == 0) return MHADA_OK;
   const long long pairs = (long long)ntok * heads;
   const size_t lds = 0;
@@ -885,6 +886,7 @@ extern "C" int mhada_vit_batch_attn(const void* qkv, void* out, int dtype, int L
                        (const uint4*)qkv, (uint4*)out, ntok, row16);
     return check_launch("mhada_vit_batch_attn");
   }
+  if (head_dim != 64) return vit_batch_attn_hd(qkv, out, dtype, L, ntok, heads, head_dim, s);  // attn_hd.hip
   if (L <= 8) {
     // bf16: the vectorised form (16-byte aligned rows in qkv and out; 97 -> 67 us at 1024^2 B4).
     // fp32 keeps the per-lane form: its vectorised instance needs ~214 VGPRs and measured

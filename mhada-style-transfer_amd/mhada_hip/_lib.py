@@ -72,6 +72,9 @@ SIGNATURES = {
     "mhada_cosine_moments": (_I, [_vp, _vp, _I, _I, _I, _I, _vp, _vp, _I, _vp]),
     "mhada_cosine_attn": (_I, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _I, _I, _I, _I, _vp]),
     "mhada_attn": (_I, [_vp] * 8 + [_I, _I, _I, _I, _I, _I, _vp]),
+    "mhada_fold_block_hd": (_I, [_vp] * 12 + [_F, _I, _I, _I, _I, _vp]),
+    "mhada_cosine_prep_hd": (_I, [_vp, _vp, _I, _I, _I, _I, _I, _I, _vp]),
+    "mhada_attn_hd": (_I, [_vp] * 7 + [_I, _I, _I, _I, _I, _I, _I, _vp]),
     "mhada_split3_kv": (_I, [_vp, _vp, _vp, _I, _I, _I, _vp]),
     "mhada_kv_proj_split3": (_I, [_vp] * 5 + [_I, _I, _I, _vp]),
     "mhada_split3_rows": (_I, [_vp, _vp, _c_ll, _vp]),
@@ -154,7 +157,7 @@ def load(path: str | None = None) -> ctypes.CDLL:
         return lib
 
 
-ABI_VERSION = 17
+ABI_VERSION = 18
 
 
 def get_tuning(name: str) -> int:

@@ -272,8 +272,10 @@ def block_forward(blk, fc: _Feat, fs: Optional[_Feat], fcs: _Feat, dt: torch.dty
     dict they are computed and stored into it (the per-style cache of adaformer_forward).
     ``want_bf16``: the out_conv GEMM also writes a bf16 copy of the block output (``.t16``) for
     the decoder's first conv (the last block of a bf16 forward)."""
+    if blk.head_dim in ops.HD_WIDTHS:
+        return _block_forward_hd(blk, fc, fs, fcs, dt, side, want_bf16)
     if blk.head_dim != HEAD_DIM:
-        raise ValueError(f"the HIP MHAda kernels implement head_dim={HEAD_DIM} (qkv_dim/num_heads), "
+        raise ValueError("the HIP MHAda kernels implement head_dim (qkv_dim/num_heads) in {32, 64, 128}, "
                          f"got {blk.head_dim}")
     prep = block_prep(blk, dt)
     H = blk.num_heads
@@ -338,6 +340,60 @@ def block_forward(blk, fc: _Feat, fs: Optional[_Feat], fcs: _Feat, dt: torch.dty
     else:
         with _timed("mhada_attn"):
             att = ops.mhada_attn(q, kv, vt, fcs.t, mu_o, rstd_o, v_mu, act)  # [B][Nc][C] dt
+    out = torch.empty(B * Nc, C, device=dev, dtype=torch.float32)
+    t16 = torch.empty(B * Nc, C, device=dev, dtype=torch.bfloat16) if want_bf16 else None
+    ops.gemm(a=att.view(B * Nc, C), w=prep["w_out"], c=out, M=B * Nc, N=C, K=C, compute=dt, lda=C, ldw=C,
+             bias=prep["b_out"], ldc=C, c2=t16, ldc2=C)
+    f = _Feat(out.view(B, Nc, C), fc.h, fc.w)
+    f.t16 = None if t16 is None else t16.view(B, Nc, C)
+    return f
+
+
+def _block_forward_hd(blk, fc: _Feat, fs: Optional[_Feat], fcs: _Feat, dt: torch.dtype,
+                      side: Optional[dict], want_bf16: bool) -> _Feat:
+    """block_forward at head_dim 32 | 128 (csrc/attn_hd.hip): fold_block_hd, the Q and K|V' projections on
+    mhada_gemm (N = K = D and N = 2D, K = D; no vt image: the attention reads kv), cosine_prep_hd for the
+    cosine activation (the flash loop, not the 64-wide linear form), attn_hd, the out_conv GEMM.  ``side``
+    caches the style-side tensors (mu_s, rstd_s, kv) exactly as on the 64 path."""
+    prep = block_prep(blk, dt)
+    H, D = blk.num_heads, blk.head_dim
+    C = H * D
+    B, Nc, Cc = fc.t.shape
+    cached = bool(side)
+    kv = None
+    act = ACT_COSINE if blk.activation_name == "cosine" else ACT_SOFTMAX
+    if cached:
+        mu_s, rstd_s, kv, Ns = side["mu_s"], side["rstd_s"], side["kv"], side["Ns"]
+        if side["B"] != B:
+            raise ValueError(f"cached style batch {side['B']} != content batch {B}")
+    else:
+        if fs.t.shape[2] != C:
+            raise ValueError(f"channel mismatch: block expects {C}")
+        mu_s, rstd_s = fs.stats()
+    if Cc != C or fcs.t.shape[2] != C:
+        raise ValueError(f"channel mismatch: block expects {C}")
+    mu_c, rstd_c = fc.stats()
+    mu_o, rstd_o = fcs.stats()
+    wq, wkv, bkv, v_mu = ops.fold_block_hd(prep["wf"], prep["wg"], prep["wh"], prep["bg"], prep["bh"],
+                                           rstd_c, mu_s, rstd_s, dt, ops.LOG2E if act == ACT_SOFTMAX else 1.0)
+    dev = fc.t.device
+    q = torch.empty(B, H, Nc, D, device=dev, dtype=dt)
+    ops.gemm(a=fc.t, w=wq, c=q, M=Nc, N=D, K=D, compute=dt, lda=C, sa=(Nc * C, D), nb=(B, H), a_mu=mu_c,
+             smu=(C, D), ldw=D, sw=(H * D * D, D * D), bias=prep["bf"], sb=(0, D), ldc=D, sc=(H * Nc * D, Nc * D))
+    if not cached:
+        Ns = fs.t.shape[1]
+        kv = torch.empty(B, H, Ns, 2 * D, device=dev, dtype=dt)
+        ops.gemm(a=fs.t, w=wkv, c=kv, M=Ns, N=2 * D, K=D, compute=dt, lda=C, sa=(Ns * C, D), nb=(B, H), a_mu=mu_s,
+                 smu=(C, D), ldw=D, sw=(H * 2 * D * D, 2 * D * D), bias=bkv, sb=(0, 2 * D), ldc=2 * D,
+                 sc=(H * Ns * 2 * D, Ns * 2 * D))
+        if act == ACT_COSINE:
+            ops.cosine_prep_hd(None, kv)
+        if side is not None:
+            side.update(mu_s=mu_s, rstd_s=rstd_s, kv=kv, Ns=Ns, B=B)
+    if act == ACT_COSINE:
+        ops.cosine_prep_hd(q, None)
+    with _timed("mhada_attn"):
+        att = ops.attn_hd(q, kv, fcs.t, mu_o, rstd_o, v_mu, act)  # [B][Nc][C] dt
     out = torch.empty(B * Nc, C, device=dev, dtype=torch.float32)
     t16 = torch.empty(B * Nc, C, device=dev, dtype=torch.bfloat16) if want_bf16 else None
     ops.gemm(a=att.view(B * Nc, C), w=prep["w_out"], c=out, M=B * Nc, N=C, K=C, compute=dt, lda=C, ldw=C,

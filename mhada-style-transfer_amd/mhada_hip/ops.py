@@ -618,6 +618,83 @@ def mhada_attn(q, kv, vt, fcs, fcs_mu, fcs_rstd, v_mu, activation: int) -> torch
     return out
 
 
+HD_WIDTHS = (32, 128)  # head widths of the *_hd entry points (csrc/attn_hd.hip); 64 has its own kernels
+
+
+def _hd_width(what: str, D: int) -> None:
+    if D not in HD_WIDTHS:
+        raise ValueError(f"{what}: head width must be 32 or 128 (64 has its own entry point), got {D}")
+
+
+def fold_block_hd(wf, wg, wh, bg, bh, rstd_c, mu_s, rstd_s, dtype: torch.dtype, kscale: float = LOG2E):
+    """``mhada_fold_block_hd``: fold_block for W* [H][D][D], D = 32 | 128."""
+    _need_gpu(wf, wg, wh, bg, bh, rstd_c, mu_s, rstd_s)
+    B, C = rstd_c.shape
+    H, D = wf.shape[0], wf.shape[1]
+    _hd_width("fold_block_hd", D)
+    for t, shape in ((wf, (H, D, D)), (wg, (H, D, D)), (wh, (H, D, D)), (bg, (H, D)), (bh, (H, D)),
+                     (rstd_c, (B, H * D)), (mu_s, (B, H * D)), (rstd_s, (B, H * D))):
+        if tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError(f"fold_block_hd: needs contiguous fp32 {shape}, got {tuple(t.shape)} {t.dtype}")
+    dt_code(dtype)
+    dev = wf.device
+    wq = torch.empty(B, H, D, D, device=dev, dtype=dtype)
+    wkv = torch.empty(B, H, 2 * D, D, device=dev, dtype=dtype)
+    bkv = torch.empty(H, 2 * D, device=dev, dtype=torch.float32)
+    v_mu = torch.empty(B, C, device=dev, dtype=torch.float32)
+    _call("mhada_fold_block_hd", wf, wf.data_ptr(), wg.data_ptr(), wh.data_ptr(), bg.data_ptr(), bh.data_ptr(),
+          rstd_c.data_ptr(), mu_s.data_ptr(), rstd_s.data_ptr(), wq.data_ptr(), wkv.data_ptr(), bkv.data_ptr(),
+          v_mu.data_ptr(), kscale, dt_code(dtype), B, H, D)
+    return wq, wkv, bkv, v_mu
+
+
+def cosine_prep_hd(q: Optional[torch.Tensor], kv: Optional[torch.Tensor]) -> None:
+    """``mhada_cosine_prep_hd``: L2-normalise the rows of q [B][H][Nc][D] and / or the K half of
+    kv [B][H][Ns][2D] in place (either may be None), D = 32 | 128."""
+    _need_gpu(q, kv)
+    if q is None and kv is None:
+        raise ValueError("cosine_prep_hd: needs q or kv")
+    ref = q if q is not None else kv
+    D = q.shape[-1] if q is not None else kv.shape[-1] // 2
+    _hd_width("cosine_prep_hd", D)
+    for t, w in ((q, D), (kv, 2 * D)):
+        if t is not None and (t.dim() != 4 or t.shape[-1] != w or t.dtype != ref.dtype or not t.is_contiguous()
+                              or t.shape[:2] != ref.shape[:2]):
+            raise ValueError(f"cosine_prep_hd: needs contiguous q [B][H][Nc][{D}] / kv [B][H][Ns][{2 * D}] of one "
+                             f"dtype, got {tuple(t.shape)} {t.dtype}")
+    B, H = ref.shape[0], ref.shape[1]
+    Nc = q.shape[2] if q is not None else 0
+    Ns = kv.shape[2] if kv is not None else 0
+    if Nc == 0 and Ns == 0:
+        return
+    _call("mhada_cosine_prep_hd", ref, _ptr(q) if Nc else None, _ptr(kv) if Ns else None, dt_code(ref.dtype), B, H,
+          D, Nc, Ns)
+
+
+def attn_hd(q, kv, fcs, fcs_mu, fcs_rstd, v_mu, activation: int) -> torch.Tensor:
+    """``mhada_attn_hd``: the fused MHAda attention at D = 32 | 128 from q [B][H][Nc][D] and kv
+    [B][H][Ns][2D] (K | V'); out [B][Nc][D H] in q's dtype."""
+    _need_gpu(q, kv, fcs, fcs_mu, fcs_rstd, v_mu)
+    if q.dim() != 4 or kv.dim() != 4:
+        raise ValueError(f"attn_hd: needs q [B][H][Nc][D] and kv [B][H][Ns][2D], got {tuple(q.shape)} / {tuple(kv.shape)}")
+    B, H, Nc, D = q.shape
+    Ns = kv.shape[2]
+    _hd_width("attn_hd", D)
+    C = H * D
+    if kv.shape != (B, H, Ns, 2 * D) or kv.dtype != q.dtype or not q.is_contiguous() or not kv.is_contiguous():
+        raise ValueError(f"attn_hd: needs contiguous q [B][H][Nc][{D}] and kv [B][H][Ns][{2 * D}] of one dtype, got "
+                         f"{tuple(q.shape)} {q.dtype} / {tuple(kv.shape)} {kv.dtype}")
+    if Nc <= 0 or Ns <= 0:
+        raise ValueError(f"attn_hd: needs Nc > 0 and Ns > 0, got {Nc} / {Ns}")
+    for t, shape in ((fcs, (B, Nc, C)), (fcs_mu, (B, C)), (fcs_rstd, (B, C)), (v_mu, (B, C))):
+        if tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError(f"attn_hd: needs contiguous fp32 {shape}, got {tuple(t.shape)} {t.dtype}")
+    out = torch.empty(B, Nc, C, device=q.device, dtype=q.dtype)
+    _call("mhada_attn_hd", q, q.data_ptr(), kv.data_ptr(), fcs.data_ptr(), fcs_mu.data_ptr(), fcs_rstd.data_ptr(),
+          v_mu.data_ptr(), out.data_ptr(), dt_code(q.dtype), B, H, D, Nc, Ns, activation)
+    return out
+
+
 # The fp32 softmax MHAda attention as SPLIT3 products on the bf16 MFMA (mhada_attn_split3): fp32-accurate
 # (against fp64 at or below the fp32 MFMA kernel's error) and faster.  False: the fp32 MFMA kernel.
 F32_SPLIT_ATTN = True
