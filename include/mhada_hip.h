@@ -330,6 +330,28 @@ int mhada_attn_train_dkv(const float* q, const float* k, const float* v, const f
                          const float* dd, float* dk, float* dv, float* ds, int BH, int Nc, int Ns,
                          mhada_stream_t stream);
 
+/* ---- training at head widths D = 32 | 128 (csrc/attn_train_hd.hip) ----------------------------
+ * Added to ABI 18 WITHOUT a version bump: the three entries below are purely additive (no existing
+ * signature, struct or knob changes), ABI 18 is the version that introduced the D-wide entry points
+ * they complete, and the binding checks the version for equality — a caller built against the
+ * earlier ABI 18 header runs unchanged; a caller that needs these entries finds them by symbol.
+ *
+ * mhada_attn_train_fwd_hd: mhada_attn_train_fwd with rows of D floats (the autograd forward of
+ *   adaDecoder.py:186-198: bmm / softmax / bmm / bmm / sqrt, per head of width D): q, x [BH][Nc][D],
+ *   k, v [BH][Ns][D] (v centred) -> out' [BH][Nc][D], mo = [M' | E2'] [BH][Nc][2D], lse [BH][Nc].
+ * mhada_attn_train_bwd_hd: mhada_attn_train_bwd with rows of D floats (the autograd backward of
+ *   adaDecoder.py:186-198): dmo [BH][Nc][2D], dd [BH][Nc] -> dq [BH][Nc][D], dk, dv [BH][Ns][D].
+ *   Two deterministic kernels, no atomics: repeated calls return the same bits.
+ * fp32 on the fp32 MFMA, A never stored.  The dS spill (mhada_attn_train_dkv), the SPLIT3 and vt
+ * forwards exist at 64 only.  Host checks before any launch: D outside {32, 128} (64 belongs to
+ * the entries above), a null pointer, BH <= 0, Nc < 0 or Ns <= 0 return MHADA_ERR_ARG; Nc == 0 is
+ * legal (dk = dv = 0).  Row offsets are 64-bit; Nc, Ns <= 2^30. */
+int mhada_attn_train_fwd_hd(const float* q, const float* k, const float* v, const float* x, float* out,
+                            float* mo, float* lse, int BH, int D, int Nc, int Ns, mhada_stream_t stream);
+int mhada_attn_train_bwd_hd(const float* q, const float* k, const float* v, const float* lse,
+                            const float* dmo, const float* dd, float* dq, float* dk, float* dv,
+                            int BH, int D, int Nc, int Ns, mhada_stream_t stream);
+
 /* Last decoder layer (conv.py:96, ConvReLU(64, 3)): ReflectionPad2d(1) + conv3x3 Cin->3 +
  * bias + ReLU on NHWC x [B][H][W][Cin] (dtype), written NCHW fp32 y [B][3][H][W] — the
  * module's output layout.  clamp255 != 0 also applies the caller's clamp(0,255)
@@ -443,6 +465,12 @@ int mhada_instnorm_bwd(const float* dy, const float* y, const float* rstd, float
  * dmo = [dM' | dVar] (rows x 128) and dd = rowsum(dM' M' + dVar E2') for mhada_attn_train_bwd. */
 int mhada_attn_train_bwd_prep(const float* dout, const float* x, const float* mo, float* dx, float* dmo,
                               float* dd, long long rows, mhada_stream_t stream);
+/* The same head with rows of D = 32 | 128 channels (mo, dmo: rows x 2D), for
+ * mhada_attn_train_bwd_hd (adaDecoder.py:189-198 under autograd, heads of width D; added to ABI 18
+ * without a bump, see mhada_attn_train_fwd_hd).  D outside {32, 128}, a null pointer or rows < 0
+ * return MHADA_ERR_ARG before any launch. */
+int mhada_attn_train_bwd_prep_hd(const float* dout, const float* x, const float* mo, float* dx, float* dmo,
+                                 float* dd, long long rows, int D, mhada_stream_t stream);
 
 int mhada_pos_embed_bwd(const float* g, float* gpos, int C, int bh, int bw, int oh, int ow,
                         mhada_stream_t stream);

@@ -716,29 +716,43 @@ __global__ void __launch_bounds__(256) inb_apply_kernel(const float* __restrict_
 }
 
 // ======================================================================================
-// MHAda attention backward head: per row (bh, query) of 64 channels, with m = M', e2 = E2':
+// MHAda attention backward head: per row (bh, query) of D channels (64, or 32 | 128 for the head
+// widths of attn_train_hd.hip), with m = M', e2 = E2':
 //   var = e2 - m^2, sd = sqrt(max(var, 1e-6)), dx = dout sd,
 //   dvar = dout x 0.5 / sd where var >= 1e-6 (0 where the clamp is active), dm = dout - 2 m dvar,
-//   dmo = [dm | dvar], dd = sum_c (dm m + dvar e2).   One wave per row, lane = channel.
+//   dmo = [dm | dvar], dd = sum_c (dm m + dvar e2).   min(D, 64) lanes per row (D = 64: one wave
+// per row, lane = channel; 32: two rows per wave; 128: channels c and c + 64 per lane), the row
+// sum a butterfly over those lanes.
 // ======================================================================================
+template <int D>
 __global__ void __launch_bounds__(256) attn_bwd_prep_kernel(const float* __restrict__ dout, const float* __restrict__ x,
                                                             const float* __restrict__ mo, float* __restrict__ dx,
                                                             float* __restrict__ dmo, float* __restrict__ dd,
                                                             long long rows) {
-  const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= rows) return;
-  const int c = threadIdx.x & 63;
-  const float m = mo[row * 128 + c], e2 = mo[row * 128 + 64 + c];
-  const float g = dout[row * 64 + c], xv = x[row * 64 + c];
-  const float var = e2 - m * m;
-  const float sd = sqrtf(fmaxf(var, 1e-6f));
-  const float dvar = var >= 1e-6f ? (g * xv) * (0.5f / sd) : 0.f;
-  const float dm = g - 2.0f * m * dvar;
-  dx[row * 64 + c] = g * sd;
-  dmo[row * 128 + c] = dm;
-  dmo[row * 128 + 64 + c] = dvar;
-  const float t = wave_sum(dm * m + dvar * e2);
-  if (c == 0) dd[row] = t;
+  constexpr int LPR = D < 64 ? D : 64;  // lanes per row
+  const long long row = (long long)blockIdx.x * (256 / LPR) + threadIdx.x / LPR;
+  const int c0 = threadIdx.x % LPR;
+  float t = 0.f;
+  if (row < rows) {
+#pragma unroll
+    for (int c = c0; c < D; c += 64) {
+      const float m = mo[row * (2 * D) + c], e2 = mo[row * (2 * D) + D + c];
+      const float g = dout[row * D + c], xv = x[row * D + c];
+      const float var = e2 - m * m;
+      const float sd = sqrtf(fmaxf(var, 1e-6f));
+      const float dvar = var >= 1e-6f ? (g * xv) * (0.5f / sd) : 0.f;
+      const float dm = g - 2.0f * m * dvar;
+      dx[row * D + c] = g * sd;
+      dmo[row * (2 * D) + c] = dm;
+      dmo[row * (2 * D) + D + c] = dvar;
+      const float u = dm * m + dvar * e2;
+      t = c == c0 ? u : t + u;
+    }
+  }
+  // (rows past the end take part with t = 0: at D = 32 a wave's two rows may straddle the end)
+#pragma unroll
+  for (int o = LPR / 2; o > 0; o >>= 1) t += __shfl_xor(t, o, 64);
+  if (c0 == 0 && row < rows) dd[row] = t;
 }
 
 // ======================================================================================
@@ -1339,9 +1353,27 @@ extern "C" int mhada_instnorm_bwd(const float* dy, const float* y, const float* 
 extern "C" int mhada_attn_train_bwd_prep(const float* dout, const float* x, const float* mo, float* dx, float* dmo,
                                          float* dd, long long rows, mhada_stream_t s_) {
   if (!dout || !x || !mo || !dx || !dmo || !dd || rows <= 0) return fail("mhada_attn_train_bwd_prep: bad args");
-  hipLaunchKernelGGL(attn_bwd_prep_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)s_, dout, x,
-                     mo, dx, dmo, dd, rows);
+  hipLaunchKernelGGL(attn_bwd_prep_kernel<64>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)s_, dout,
+                     x, mo, dx, dmo, dd, rows);
   return check_launch("mhada_attn_train_bwd_prep");
+}
+
+extern "C" int mhada_attn_train_bwd_prep_hd(const float* dout, const float* x, const float* mo, float* dx, float* dmo,
+                                            float* dd, long long rows, int D, mhada_stream_t s_) {
+  if (!dout || !x || !mo || !dx || !dmo || !dd || rows < 0) return fail("mhada_attn_train_bwd_prep_hd: bad args");
+  if (D != 32 && D != 128)
+    return fail("mhada_attn_train_bwd_prep_hd: D must be 32 or 128 (64: mhada_attn_train_bwd_prep)");
+  if (rows == 0) return MHADA_OK;
+  const int rpb = D == 32 ? 8 : 4;  // rows per block
+  const long long nblk = (rows + rpb - 1) / rpb;
+  if (nblk > (1LL << 31) - 1) return fail("mhada_attn_train_bwd_prep_hd: grid too large");
+  if (D == 32)
+    hipLaunchKernelGGL(attn_bwd_prep_kernel<32>, dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)s_, dout, x, mo, dx,
+                       dmo, dd, rows);
+  else
+    hipLaunchKernelGGL(attn_bwd_prep_kernel<128>, dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)s_, dout, x, mo,
+                       dx, dmo, dd, rows);
+  return check_launch("mhada_attn_train_bwd_prep_hd");
 }
 
 extern "C" int mhada_pos_embed_bwd(const float* g, float* gpos, int C, int bh, int bw, int oh, int ow,

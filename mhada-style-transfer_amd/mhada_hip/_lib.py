@@ -88,6 +88,8 @@ SIGNATURES = {
     "mhada_transpose64_split3": (_I, [_vp, _vp, _I, _I, _I, _vp]),
     "mhada_attn_train_bwd": (_I, [_vp] * 9 + [_I, _I, _I, _vp]),
     "mhada_attn_train_dkv": (_I, [_vp] * 9 + [_I, _I, _I, _vp]),
+    "mhada_attn_train_fwd_hd": (_I, [_vp] * 7 + [_I, _I, _I, _I, _vp]),
+    "mhada_attn_train_bwd_hd": (_I, [_vp] * 9 + [_I, _I, _I, _I, _vp]),
     "mhada_conv3x3_out3": (_I, [_vp, _I, _vp, _vp, _vp, _I, _I, _I, _I, _I, _vp]),
     "mhada_upsample2x": (_I, [_vp, _vp, _I, _I, _I, _I, _I, _vp]),
     "mhada_warp": (_I, [_vp, _vp, _vp, _I, _I, _I, _I, _I, _vp]),
@@ -106,6 +108,7 @@ SIGNATURES = {
     "mhada_pos_embed_bwd": (_I, [_vp, _vp, _I, _I, _I, _I, _I, _vp]),
     "mhada_instnorm_bwd": (_I, [_vp, _vp, _vp, _vp, _vp, _I, _I, _I, _I, _vp]),
     "mhada_attn_train_bwd_prep": (_I, [_vp, _vp, _vp, _vp, _vp, _vp, _c_ll, _vp]),
+    "mhada_attn_train_bwd_prep_hd": (_I, [_vp, _vp, _vp, _vp, _vp, _vp, _c_ll, _I, _vp]),
     "mhada_vit_batch_attn_bwd": (_I, [_vp, _vp, _vp, _I, _I, _I, _I, _vp]),
     "mhada_vit_batch_attn_bwd_split3": (_I, [_vp, _vp, _vp, _vp, _c_ll, _I, _I, _I, _I, _vp]),
     "mhada_relu_bwd": (_I, [_vp, _vp, _vp, _c_ll, _vp]),

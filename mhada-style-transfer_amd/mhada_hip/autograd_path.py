@@ -124,15 +124,17 @@ def _softmax_or_cosine(q, k, activation: str):
 
 class MHAdaAttnFn(torch.autograd.Function):
     """The attention core of adaDecoder.py:186-198 on the HIP training kernels
-    (csrc/attn_train.hip): out' = sqrt(max(E2' - M'^2, 1e-6)) * x + M' with M' = A V',
-    E2' = A V'^2, A = softmax(q k^T).  q, x (BH, Nc, 64); k, v (BH, Ns, 64), v centred.
+    (csrc/attn_train.hip; head widths 32 and 128: csrc/attn_train_hd.hip):
+    out' = sqrt(max(E2' - M'^2, 1e-6)) * x + M' with M' = A V', E2' = A V'^2, A = softmax(q k^T).
+    q, x (BH, Nc, D); k, v (BH, Ns, D), v centred, D = 64 | 32 | 128.
     A is never stored: the backward recomputes it from the saved row normaliser."""
 
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
     def forward(ctx, q, k, v, x):
         q, k, v, x = (t.contiguous() for t in (q, k, v, x))
-        out, mo, lse = ops.attn_train_fwd(q, k, v, x)
+        fwd = ops.attn_train_fwd if q.shape[-1] == 64 else ops.attn_train_fwd_hd
+        out, mo, lse = fwd(q, k, v, x)
         ctx.save_for_backward(q, k, v, x, mo, lse)
         return out
 
@@ -142,8 +144,12 @@ class MHAdaAttnFn(torch.autograd.Function):
         q, k, v, x, mo, lse = ctx.saved_tensors
         # S = sqrt(max(E2' - M'^2, 1e-6)), out' = S x + M': dx = dout S, dVar = dout x / (2 S) where
         # the clamp is inactive, dM' = dout - 2 M' dVar, dd = rowsum(dM' M' + dVar E2')  (one kernel)
-        dx, dmo, dd = ops.attn_train_bwd_prep(dout.contiguous(), x, mo)
-        dq, dk, dv = ops.attn_train_bwd(q, k, v, lse, dmo, dd)
+        if q.shape[-1] == 64:
+            dx, dmo, dd = ops.attn_train_bwd_prep(dout.contiguous(), x, mo)
+            dq, dk, dv = ops.attn_train_bwd(q, k, v, lse, dmo, dd)
+        else:
+            dx, dmo, dd = ops.attn_train_bwd_prep_hd(dout.contiguous(), x, mo)
+            dq, dk, dv = ops.attn_train_bwd_hd(q, k, v, lse, dmo, dd)
         return dq, dk, dv, dx
 
 
@@ -151,17 +157,19 @@ def _fused_train_attn(blk, fc) -> bool:
     """The HIP training kernels compute in fp32.  An fp32 input takes this path; so does any
     floating input inside a CUDA autocast region (MHAdaAttnFn's custom_fwd casts its operands to
     fp32 there).  Outside autocast a bf16 / fp16 / fp64 block input (model.half(), a gradcheck)
-    runs the aten formula: the token-path statistics kernels read fp32 only."""
+    runs the aten formula: the token-path statistics kernels read fp32 only.  Head widths 64 (8 heads
+    at 512 channels), 32 and 128 (16 and 4 heads) have kernels; any other width, and the cosine
+    activation, keep the aten path of block_forward."""
     return (fc.is_cuda and (fc.dtype == torch.float32 or (fc.is_floating_point() and torch.is_autocast_enabled("cuda")))
-            and blk.activation_name == "softmax" and blk.head_dim == 64 and TRAIN_ATTN != "torch")
+            and blk.activation_name == "softmax" and blk.head_dim in (32, 64, 128) and TRAIN_ATTN != "torch")
 
 
 def _head_proj(mods, t: torch.Tensor, H: int) -> torch.Tensor:
     """Per-head 1x1 convs (adaDecoder.py:188-190, f/g/h_list[i] on channel slice i) on the
     modules' own parameters.  On a ROCm device: ONE grouped GEMM over the heads on the HIP
     kernels (train_fns.head_proj; the gradients reach each head's weight through torch.stack),
-    (B, 64H, h, w) -> (H*B, h*w, 64) in HEAD-major order.  On the CPU: a head-batched matmul,
-    (B*H, h*w, 64) batch-major.  The attention core treats (head, batch) pairs independently;
+    (B, dH, h, w) -> (H*B, h*w, d) in HEAD-major order.  On the CPU: a head-batched matmul,
+    (B*H, h*w, d) batch-major.  The attention core treats (head, batch) pairs independently;
     _heads_rows and the out_conv gather follow the same order."""
     B, C, h, w = t.shape
     d = C // H
@@ -178,7 +186,7 @@ def _head_proj(mods, t: torch.Tensor, H: int) -> torch.Tensor:
 
 
 def _heads_rows(t: torch.Tensor, H: int, head_major: bool = False) -> torch.Tensor:
-    """(B, 64H, h, w) -> (B*H, h*w, 64) contiguous, batch-major or (head_major) (H*B, ...)."""
+    """(B, dH, h, w) -> (B*H, h*w, d) contiguous, batch-major or (head_major) (H*B, ...)."""
     B, C, h, w = t.shape
     if head_major:
         return t.reshape(B, H, C // H, h * w).permute(1, 0, 3, 2).reshape(H * B, h * w, C // H).contiguous()

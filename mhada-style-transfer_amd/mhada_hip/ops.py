@@ -486,6 +486,21 @@ def attn_train_bwd_prep(dout: torch.Tensor, x: torch.Tensor, mo: torch.Tensor):
     return dx, dmo, dd
 
 
+def attn_train_bwd_prep_hd(dout: torch.Tensor, x: torch.Tensor, mo: torch.Tensor):
+    """``mhada_attn_train_bwd_prep_hd``: ``attn_train_bwd_prep`` with rows of D = 32 | 128 channels."""
+    _rows64(dout, x, mo)
+    D = _train_hd_width("attn_train_bwd_prep_hd", x)
+    BH, Nc, _ = x.shape
+    if dout.shape != x.shape or mo.shape != (BH, Nc, 2 * D):
+        raise ValueError("attn_train_bwd_prep_hd: bad shapes")
+    dx = torch.empty_like(x)
+    dmo = torch.empty_like(mo)
+    dd = torch.empty(BH, Nc, device=x.device, dtype=torch.float32)
+    _call("mhada_attn_train_bwd_prep_hd", x, dout.data_ptr(), x.data_ptr(), mo.data_ptr(), dx.data_ptr(),
+          dmo.data_ptr(), dd.data_ptr(), BH * Nc, D)
+    return dx, dmo, dd
+
+
 def layernorm_fwd(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float, planes: bool = False):
     """``mhada_layernorm_fwd``: fp32 rows [M][C] -> (y fp32, stats [M][2]); ``planes``: also y's three bf16
     planes [3][M][C] (``mhada_layernorm_fwd_split3``) -> (y, stats, planes)."""
@@ -872,6 +887,51 @@ def attn_train_bwd(q, k, v, lse, dmo, dd, spill: Optional[bool] = None):
         ldt = kt.shape[-1]
         gemm(a=ds, w=kt, c=dq, M=Nc, N=64, K=Ns, compute=torch.float32, lda=Ns, sa=(Nc * Ns, 0), nb=(BH, 1),
              ldw=ldt, sw=(64 * ldt, 0), ldc=64, sc=(Nc * 64, 0))
+    return dq, dk, dv
+
+
+def _train_hd_width(what: str, t: torch.Tensor) -> int:
+    D = t.shape[-1] if t.dim() == 3 else -1
+    if D not in (32, 128):
+        raise ValueError(f"{what}: rows of 32 or 128 floats (64: the op without _hd), got {tuple(t.shape)}")
+    return D
+
+
+def attn_train_fwd_hd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, x: torch.Tensor):
+    """``mhada_attn_train_fwd_hd``: ``attn_train_fwd`` at head width D = 32 | 128 (csrc/attn_train_hd.hip):
+    q, x (BH, Nc, D); k, v (BH, Ns, D) with v centred.  Returns out' (BH, Nc, D), [M' | E2'] (BH, Nc, 2D),
+    lse2 (BH, Nc).  One fp32-MFMA kernel; the TRAIN_FWD_* knobs are 64-wide only."""
+    _rows64(q, k, v, x)
+    D = _train_hd_width("attn_train_fwd_hd", q)
+    BH, Nc, _ = q.shape
+    Ns = k.shape[1] if k.dim() == 3 else -1
+    if k.shape != (BH, Ns, D) or v.shape != k.shape or x.shape != q.shape or Ns <= 0:
+        raise ValueError(f"attn_train_fwd_hd: bad shapes q{tuple(q.shape)} k{tuple(k.shape)} v{tuple(v.shape)} "
+                         f"x{tuple(x.shape)}")
+    out = torch.empty_like(q)
+    mo = torch.empty(BH, Nc, 2 * D, device=q.device, dtype=torch.float32)
+    lse = torch.empty(BH, Nc, device=q.device, dtype=torch.float32)
+    _call("mhada_attn_train_fwd_hd", q, q.data_ptr(), k.data_ptr(), v.data_ptr(), x.data_ptr(), out.data_ptr(),
+          mo.data_ptr(), lse.data_ptr(), BH, D, Nc, Ns)
+    return out, mo, lse
+
+
+def attn_train_bwd_hd(q, k, v, lse, dmo, dd):
+    """``mhada_attn_train_bwd_hd``: ``attn_train_bwd`` at head width D = 32 | 128: returns dq (BH, Nc, D),
+    dk, dv (BH, Ns, D).  Always the recompute backward (no dS spill at these widths, no workspace);
+    BWD_PATH_COUNTS counts the 64-wide paths only."""
+    _rows64(q, k, v, lse, dmo, dd)
+    D = _train_hd_width("attn_train_bwd_hd", q)
+    BH, Nc, _ = q.shape
+    Ns = k.shape[1] if k.dim() == 3 else -1
+    if lse.shape != (BH, Nc) or dmo.shape != (BH, Nc, 2 * D) or dd.shape != (BH, Nc) or k.shape != (BH, Ns, D) \
+            or v.shape != k.shape or Ns <= 0:
+        raise ValueError("attn_train_bwd_hd: bad shapes")
+    dq = torch.empty_like(q)
+    dk = torch.empty_like(k)
+    dv = torch.empty_like(v)
+    _call("mhada_attn_train_bwd_hd", q, q.data_ptr(), k.data_ptr(), v.data_ptr(), lse.data_ptr(), dmo.data_ptr(),
+          dd.data_ptr(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), BH, D, Nc, Ns)
     return dq, dk, dv
 
 

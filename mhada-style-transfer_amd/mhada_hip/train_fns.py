@@ -371,24 +371,25 @@ def pos_embed(pos: torch.Tensor, h: int, w: int) -> torch.Tensor:
 
 class HeadProjFn(torch.autograd.Function):
     """The per-head 1x1 convs of AdaAttnMultiHead (adaDecoder.py:143-145,188-190: f/g/h_list[i] on
-    channel slice i) as ONE grouped GEMM over the heads: token rows x [T][H*64], stacked weights
-    [H][64][64] and biases [H][64] -> y [H][T][64] (head-major: the (head, batch) order the
-    training attention takes).  Backward: dX as the grouped GEMM with the transposed head weights
-    (written straight into each head's column block), dW per head on the TN kernel, db a column
-    sum.  1/8 of the block-diagonal 512x512 product's FLOPs in each direction."""
+    channel slice i) as ONE grouped GEMM over the heads: token rows x [T][H*d], stacked weights
+    [H][d][d] and biases [H][d] -> y [H][T][d] (head-major: the (head, batch) order the
+    training attention takes), d = 32 | 64 | 128.  Backward: dX as the grouped GEMM with the
+    transposed head weights (written straight into each head's column block), dW per head on the TN
+    kernel, db a column sum.  1/H of the block-diagonal product's FLOPs in each direction.  The
+    fp32 GEMM forms: d = 32 and 64 the N <= 64 LDS-DMA ring kernel, d = 128 the 128 x 128 tile."""
 
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
     def forward(ctx, x, weight, bias):
         x = x.contiguous()
         T, C = x.shape
-        H = weight.shape[0]
-        if C != 64 * H or weight.shape[1:] != (64, 64):
-            raise ValueError("HeadProjFn: x [T][64H], weight [H][64][64]")
-        y = torch.empty(H, T, 64, device=x.device, dtype=F32)
-        ops.gemm(a=x, w=weight.detach().contiguous(), c=y, M=T, N=64, K=64, compute=F32, lda=C, sa=(64, 0),
-                 nb=(H, 1), ldw=64, sw=(4096, 0), bias=bias.detach().contiguous(), sb=(64, 0), ldc=64,
-                 sc=(T * 64, 0))
+        H, d = weight.shape[0], weight.shape[-1]
+        if d not in (32, 64, 128) or C != d * H or weight.shape[1:] != (d, d):
+            raise ValueError("HeadProjFn: x [T][d H], weight [H][d][d] with d = 32, 64 or 128")
+        y = torch.empty(H, T, d, device=x.device, dtype=F32)
+        ops.gemm(a=x, w=weight.detach().contiguous(), c=y, M=T, N=d, K=d, compute=F32, lda=C, sa=(d, 0),
+                 nb=(H, 1), ldw=d, sw=(d * d, 0), bias=bias.detach().contiguous(), sb=(d, 0), ldc=d,
+                 sc=(T * d, 0))
         ctx.save_for_backward(x, weight)
         return y
 
@@ -397,18 +398,18 @@ class HeadProjFn(torch.autograd.Function):
     def backward(ctx, gy):
         x, weight = ctx.saved_tensors
         T, C = x.shape
-        H = weight.shape[0]
+        H, d = weight.shape[0], weight.shape[-1]
         gy = gy.contiguous()
         gx = gw = gb = None
         if ctx.needs_input_grad[0]:
             gx = torch.empty(T, C, device=x.device, dtype=F32)
-            ops.gemm(a=gy, w=weight.detach().transpose(1, 2).contiguous(), c=gx, M=T, N=64, K=64, compute=F32,
-                     lda=64, sa=(T * 64, 0), nb=(H, 1), ldw=64, sw=(4096, 0), ldc=C, sc=(64, 0))
+            ops.gemm(a=gy, w=weight.detach().transpose(1, 2).contiguous(), c=gx, M=T, N=d, K=d, compute=F32,
+                     lda=d, sa=(T * d, 0), nb=(H, 1), ldw=d, sw=(d * d, 0), ldc=C, sc=(d, 0))
         if ctx.needs_input_grad[1]:
-            # all heads in one batched TN launch (head i: A = gy[i], B = x[:, 64i:]), the bias
+            # all heads in one batched TN launch (head i: A = gy[i], B = x[:, d i:]), the bias
             # gradients from the same pass
-            gw, cs = ops.gemm_tn(gy, x, M=64, N=64, K=T, lda=64, ldb=C, b_mode=A_ROWS, colsum=True, nb=H,
-                                 sza=T * 64, szb=64)
+            gw, cs = ops.gemm_tn(gy, x, M=d, N=d, K=T, lda=d, ldb=C, b_mode=A_ROWS, colsum=True, nb=H,
+                                 sza=T * d, szb=d)
             if ctx.needs_input_grad[2]:
                 gb = cs
         elif ctx.needs_input_grad[2]:
