@@ -132,11 +132,13 @@ __global__ void __launch_bounds__(64 * W) loss_attn_kernel(const LossAttnP p) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int key = key0 + (r & 3) + 8 * (r >> 2) + 4 * h;
-        S[r] *= kLog2e;
         if (key0 + 32 > p.Ns && key >= p.Ns) S[r] = -INFINITY;  // uniform test first: tail tile only
         mx = fmaxf(mx, S[r]);
       }
-      mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+      // the max on the raw scores, then P = exp2(s log2 e - m2) as one fma per score, as the LDS form
+      // below: scaling s first rounds the exponent at |s log2 e| 2^-24 BEFORE the max is subtracted, a
+      // relative error of that size between weights of different levels (tests/test_gpu_attn_forms.py)
+      mx = fmaxf(mx, __shfl_xor(mx, 32, 64)) * kLog2e;
       if (mx > m2 + kLossRescaleThr || tt == 0) {  // per-lane (query) decision; O rows are per query
         const float mn = fmaxf(m2, mx);
         const float alpha = m2 == -INFINITY ? 0.f : __builtin_amdgcn_exp2f(m2 - mn);
@@ -150,7 +152,7 @@ __global__ void __launch_bounds__(64 * W) loss_attn_kernel(const LossAttnP p) {
       float sum = 0.f;
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        S[r] = __builtin_amdgcn_exp2f(S[r] - m2);  // bare v_exp_f32 (no denormal range fix-up)
+        S[r] = __builtin_amdgcn_exp2f(fmaf(S[r], kLog2e, -m2));  // bare v_exp_f32 (no denormal range fix-up)
         sum += S[r];
       }
       l += sum;
