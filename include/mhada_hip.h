@@ -352,6 +352,47 @@ int mhada_attn_train_bwd_hd(const float* q, const float* k, const float* v, cons
                             const float* dmo, const float* dd, float* dq, float* dk, float* dv,
                             int BH, int D, int Nc, int Ns, mhada_stream_t stream);
 
+/* ---- bf16 training attention at head width 64 (csrc/attn_train_bf16.hip) ------------------------
+ * Added to ABI 18 WITHOUT a version bump, for the reasons given for the _hd entries above: the
+ * three entries are purely additive and are found by symbol.
+ *
+ * The opt-in mixed-precision form of mhada_attn_train_fwd / mhada_attn_train_bwd (adaDecoder.py:
+ * 186-198 under torch.autocast(bfloat16): bmm in bf16, softmax in fp32): the same fp32 tensors in
+ * and out with the _hd pair's pointer and shape conventions at D = 64, the three attention
+ * products of each direction on the bf16 MFMA with fp32 accumulation.  bf16 (round to nearest
+ * even): Q, K, V'_b = bf16(V'), P, dM', dE2', dS; V'_b^2 enters as an exact hi + lo pair of bf16
+ * planes (so E2' - M'^2 is the variance of V'_b to fp32 accuracy, and the backward differentiates
+ * exactly that), and dM', dE2' enter the two cancelling terms of dV' as hi + lo planes; fp32: the logits
+ * S = (bf16 Q . bf16 K) log2(e), the online softmax, the row sum, lse2, D_row, dA - D_row and
+ * every accumulator.  Forward and backward form S identically, so the backward's recomputed P is
+ * the forward's.  dmo comes from mhada_attn_train_bwd_prep (unchanged: mo stays fp32), but not
+ * D_row: the backward takes the forward's mo instead of prep's dd and forms D_row = sum_c
+ * bf16(dmo) mo itself, from the rounded dmo its dA is formed from — dS = P (dA - D_row) cancels
+ * where the softmax is peaked, and the D_row of the unrounded dmo leaves bf16-eps |dA| there.  Two
+ * deterministic backward kernels, no atomics, no dS spill; the Nc x Ns matrices never reach memory.
+ *
+ * ws: a device workspace of at least mhada_attn_train_bf16_workspace(BH, Nc, Ns, backward) bytes
+ * (backward = 0: the forward's, 1: the backward's; -1 for bad sizes), 16-byte aligned, owned by
+ * the caller — the library never allocates.  A pre-pass writes the operands' bf16 row and
+ * transposed images there once per call (forward: Q, K, V'^T, V'^2^T hi / lo; backward: Q, Q^T, K,
+ * K^T, V', V'^2 hi / lo, dmo, dmo^T hi / lo, D_row); its contents are undefined afterwards.
+ * mhada_attn_train_bwd_bf16's `phases`: 3 = the whole backward; 1 = the pre-pass only (fills ws
+ * from q, k, v, dmo, mo; lse, dq, dk, dv may be NULL); 2 = the kernels only, on a ws that a
+ * phases = 1 call with the same sizes filled (dmo, mo may be NULL) — a caller that splits the call
+ * can release dmo in between, which keeps the peak of one block's forward + backward at
+ * Nc = Ns = 1024 below one Nc x Ns fp32 matrix.
+ * Host checks before any launch: a null pointer, BH <= 0, Nc < 0, Ns <= 0, Nc or Ns above 2^30, a
+ * workspace unaligned or too small return MHADA_ERR_ARG; Nc == 0 is legal (dk = dv = 0).  Row
+ * offsets are 64-bit. */
+long long mhada_attn_train_bf16_workspace(int BH, int Nc, int Ns, int backward);
+int mhada_attn_train_fwd_bf16(const float* q, const float* k, const float* v, const float* x, float* out,
+                              float* mo, float* lse, void* ws, long long ws_size, int BH, int Nc, int Ns,
+                              mhada_stream_t stream);
+int mhada_attn_train_bwd_bf16(const float* q, const float* k, const float* v, const float* lse,
+                              const float* dmo, const float* mo, float* dq, float* dk, float* dv,
+                              void* ws, long long ws_size, int BH, int Nc, int Ns, int phases,
+                              mhada_stream_t stream);
+
 /* Last decoder layer (conv.py:96, ConvReLU(64, 3)): ReflectionPad2d(1) + conv3x3 Cin->3 +
  * bias + ReLU on NHWC x [B][H][W][Cin] (dtype), written NCHW fp32 y [B][3][H][W] — the
  * module's output layout.  clamp255 != 0 also applies the caller's clamp(0,255)

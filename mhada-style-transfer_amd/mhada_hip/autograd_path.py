@@ -13,6 +13,7 @@ whose state_dict keys match the reference), so autograd reaches exactly those pa
 """
 from __future__ import annotations
 
+import contextlib
 from typing import Dict, List, Sequence
 
 import torch
@@ -20,8 +21,24 @@ import torch.nn.functional as F
 
 from . import ops
 
-# "hip": the MHAda attention core trains on the HIP kernels; "torch": plain autograd (A/B, tests)
+# "hip": the MHAda attention core trains on the fp32 HIP kernels; "bf16": at head width 64 with
+# softmax, on the bf16-MFMA kernels (MHAdaAttnBf16Fn; every other block as "hip"); "torch": plain
+# autograd (A/B, tests).  Trainer(attn_precision="bf16") selects "bf16" around its forward passes
+# (train_attn); the backward follows the function the forward chose.
 TRAIN_ATTN = "hip"
+
+
+@contextlib.contextmanager
+def train_attn(mode: str):
+    """Run the enclosed forward passes with TRAIN_ATTN = ``mode``; restores the previous value."""
+    global TRAIN_ATTN
+    if mode not in ("hip", "bf16", "torch"):
+        raise ValueError(f"train_attn: mode must be 'hip', 'bf16' or 'torch', got {mode!r}")
+    saved, TRAIN_ATTN = TRAIN_ATTN, mode
+    try:
+        yield
+    finally:
+        TRAIN_ATTN = saved
 
 # decoder layers and whether bilinear x2 follows them (conv.py:78-94)
 DECODER_ORDER = (("conv1", 0, True), ("conv1", 1, False), ("conv1", 2, False), ("conv1", 3, False),
@@ -153,6 +170,35 @@ class MHAdaAttnFn(torch.autograd.Function):
         return dq, dk, dv, dx
 
 
+class MHAdaAttnBf16Fn(torch.autograd.Function):
+    """MHAdaAttnFn at head width 64 with the three attention products of each direction on the bf16
+    MFMA (csrc/attn_train_bf16.hip): fp32 tensors in and out, bf16 Q, K, V', P, dM', dE2', dS (the
+    square of the rounded V' as an exact hi + lo pair, dM' / dE2' as hi + lo where dV' cancels),
+    fp32 logits, softmax, statistics and accumulation — what the reference's own code computes under
+    torch.autocast(bfloat16), with the logits kept in fp32.  The elementwise head of the backward is
+    MHAdaAttnFn's (mo stays fp32) except D_row, which the library forms from the rounded dmo
+    (ops.attn_train_bwd_bf16); the backward recomputes S and dA (no dS spill)."""
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
+    def forward(ctx, q, k, v, x):
+        q, k, v, x = (t.contiguous() for t in (q, k, v, x))
+        out, mo, lse = ops.attn_train_fwd_bf16(q, k, v, x)
+        ctx.save_for_backward(q, k, v, x, mo, lse)
+        return out
+
+    @staticmethod
+    @torch.amp.custom_bwd(device_type="cuda")
+    def backward(ctx, dout):
+        q, k, v, x, mo, lse = ctx.saved_tensors
+        dx, dmo, _ = ops.attn_train_bwd_prep(dout.contiguous(), x, mo)
+        # ops.attn_train_bwd_bf16 in its two phases: dmo is dead once its bf16 images are written
+        ws = ops.attn_train_bwd_bf16_prepass(q, k, v, dmo, mo)
+        del dmo
+        dq, dk, dv = ops.attn_train_bwd_bf16_run(q, k, v, lse, ws)
+        return dq, dk, dv, dx
+
+
 def _fused_train_attn(blk, fc) -> bool:
     """The HIP training kernels compute in fp32.  An fp32 input takes this path; so does any
     floating input inside a CUDA autocast region (MHAdaAttnFn's custom_fwd casts its operands to
@@ -226,7 +272,9 @@ def block_forward_fused(blk, fc: torch.Tensor, fs: torch.Tensor, fcs: torch.Tens
     # detached — its gradient terms (sum over Nc of dout, minus the mean of dv) are exact zeros the
     # backward would otherwise spend five kernels per block on
     vmu = v.detach().mean(dim=1, keepdim=True)
-    o = MHAdaAttnFn.apply(q, k, (v - vmu).contiguous(), x) + vmu
+    # TRAIN_ATTN "bf16": head width 64 only (this path is softmax only); 32 and 128 keep the fp32 kernels
+    fn = MHAdaAttnBf16Fn if TRAIN_ATTN == "bf16" and fc.is_cuda and q.shape[-1] == 64 else MHAdaAttnFn
+    o = fn.apply(q, k, (v - vmu).contiguous(), x) + vmu
     if fc.is_cuda:  # out_conv (1x1) as a token GEMM on the HIP kernels
         from . import train_fns
         rows = o.view(H, B * h * w, C // H).permute(1, 0, 2).reshape(B * h * w, C)

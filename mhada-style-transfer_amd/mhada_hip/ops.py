@@ -935,6 +935,87 @@ def attn_train_bwd_hd(q, k, v, lse, dmo, dd):
     return dq, dk, dv
 
 
+# Calls of the bf16 training attention (attn_train_fwd_bf16 / attn_train_bwd_bf16): tests and tools
+# read it, as BWD_PATH_COUNTS for the fp32 paths (which these calls do not touch).
+BF16_TRAIN_COUNTS = {"fwd": 0, "bwd": 0}
+
+
+def _bf16_workspace(q: torch.Tensor, BH: int, Nc: int, Ns: int, backward: bool) -> torch.Tensor:
+    n = _lib.load().mhada_attn_train_bf16_workspace(BH, Nc, Ns, int(backward))
+    if n < 0:
+        raise ValueError("attn_train_bf16: bad sizes")
+    return torch.empty(max(n, 16), device=q.device, dtype=torch.uint8)
+
+
+def attn_train_fwd_bf16(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, x: torch.Tensor):
+    """``mhada_attn_train_fwd_bf16``: ``attn_train_fwd`` with Q K^T, P V' and P V'^2 on the bf16 MFMA
+    (csrc/attn_train_bf16.hip; fp32 accumulation and softmax): fp32 q, x (BH, Nc, 64); k, v (BH, Ns, 64)
+    with v centred.  Returns fp32 out' (BH, Nc, 64), [M' | E2'] (BH, Nc, 128), lse2 (BH, Nc).  The bf16
+    operand images live in a workspace freed after the call."""
+    _rows64(q, k, v, x)
+    BH, Nc, d = q.shape if q.dim() == 3 else (0, 0, 0)
+    Ns = k.shape[1] if k.dim() == 3 else -1
+    if d != 64 or k.shape != (BH, Ns, 64) or v.shape != k.shape or x.shape != q.shape or Ns <= 0:
+        raise ValueError(f"attn_train_fwd_bf16: bad shapes q{tuple(q.shape)} k{tuple(k.shape)} v{tuple(v.shape)} "
+                         f"x{tuple(x.shape)}")
+    out = torch.empty_like(q)
+    mo = torch.empty(BH, Nc, 128, device=q.device, dtype=torch.float32)
+    lse = torch.empty(BH, Nc, device=q.device, dtype=torch.float32)
+    ws = _bf16_workspace(q, BH, Nc, Ns, False)
+    BF16_TRAIN_COUNTS["fwd"] += 1
+    _call("mhada_attn_train_fwd_bf16", q, q.data_ptr(), k.data_ptr(), v.data_ptr(), x.data_ptr(), out.data_ptr(),
+          mo.data_ptr(), lse.data_ptr(), ws.data_ptr(), ws.numel(), BH, Nc, Ns)
+    return out, mo, lse
+
+
+def attn_train_bwd_bf16_prepass(q, k, v, dmo, mo) -> torch.Tensor:
+    """Phase 1 of ``mhada_attn_train_bwd_bf16``: the bf16 operand images and D_row = sum_c bf16(dmo) mo
+    of the backward, written into a new workspace that ``attn_train_bwd_bf16_run`` consumes.  dmo is
+    dead afterwards: a caller that drops it before the run keeps the peak memory lower
+    (MHAdaAttnBf16Fn.backward)."""
+    _rows64(q, k, v, dmo, mo)
+    BH, Nc, d = q.shape if q.dim() == 3 else (0, 0, 0)
+    Ns = k.shape[1] if k.dim() == 3 else -1
+    if d != 64 or dmo.shape != (BH, Nc, 128) or mo.shape != dmo.shape or k.shape != (BH, Ns, 64) \
+            or v.shape != k.shape or Ns <= 0:
+        raise ValueError("attn_train_bwd_bf16: bad shapes")
+    ws = _bf16_workspace(q, BH, Nc, Ns, True)
+    _call("mhada_attn_train_bwd_bf16", q, q.data_ptr(), k.data_ptr(), v.data_ptr(), None, dmo.data_ptr(),
+          mo.data_ptr(), None, None, None, ws.data_ptr(), ws.numel(), BH, Nc, Ns, 1)
+    return ws
+
+
+def attn_train_bwd_bf16_run(q, k, v, lse, ws: torch.Tensor):
+    """Phase 2 of ``mhada_attn_train_bwd_bf16``: the dQ and dK / dV' kernels on the workspace of
+    ``attn_train_bwd_bf16_prepass`` (same q, k, v).  Returns fp32 dq (BH, Nc, 64), dk, dv (BH, Ns, 64)."""
+    _rows64(q, k, v, lse)
+    _need_gpu(ws)
+    BH, Nc, d = q.shape if q.dim() == 3 else (0, 0, 0)
+    Ns = k.shape[1] if k.dim() == 3 else -1
+    if d != 64 or lse.shape != (BH, Nc) or k.shape != (BH, Ns, 64) or v.shape != k.shape or Ns <= 0 \
+            or ws.dtype != torch.uint8:
+        raise ValueError("attn_train_bwd_bf16: bad shapes")
+    dq = torch.empty_like(q)
+    dk = torch.empty_like(k)
+    dv = torch.empty_like(v)
+    BF16_TRAIN_COUNTS["bwd"] += 1
+    _call("mhada_attn_train_bwd_bf16", q, q.data_ptr(), k.data_ptr(), v.data_ptr(), lse.data_ptr(), None, None,
+          dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), ws.data_ptr(), ws.numel(), BH, Nc, Ns, 2)
+    return dq, dk, dv
+
+
+def attn_train_bwd_bf16(q, k, v, lse, dmo, mo):
+    """``mhada_attn_train_bwd_bf16``: ``attn_train_bwd`` on the bf16 MFMA (the recompute form: a
+    query-stationary dQ kernel and a key-stationary dK / dV' kernel, no dS spill, no SPLIT3 GEMM):
+    fp32 operands of ``attn_train_bwd``'s shapes, returns fp32 dq (BH, Nc, 64), dk, dv (BH, Ns, 64).
+    Where ``attn_train_bwd`` takes D_row (``attn_train_bwd_prep``'s dd) this takes the forward's
+    ``mo`` (BH, Nc, 128): the library forms D_row = sum_c bf16(dmo) mo from the rounded dmo it
+    multiplies with, so that dS = P (dA - D_row) cancels where the softmax is peaked.
+    = ``attn_train_bwd_bf16_prepass`` + ``attn_train_bwd_bf16_run``."""
+    _rows64(lse)
+    return attn_train_bwd_bf16_run(q, k, v, lse, attn_train_bwd_bf16_prepass(q, k, v, dmo, mo))
+
+
 # dQ = dS K of the dS-spill backward as SPLIT3 products on the bf16 MFMA (csrc/gemm_n64_split3.hip,
 # round 6) where Ns % 32 == 0; False: the fp32-MFMA N <= 64 GEMM (gemm_n64_kernel)
 TRAIN_DQ_S3 = True

@@ -10,6 +10,7 @@ Checkpoints use the reference's dict layout (train_image.py:172-186).
 """
 from __future__ import annotations
 
+import contextlib
 from typing import Dict, Optional
 
 import torch
@@ -26,8 +27,15 @@ VIDEO_LAMBDA_ID1, VIDEO_LAMBDA_ID2 = 5e-2, 1e-1
 
 class Trainer:
     def __init__(self, vit_c: nn.Module, vit_s: nn.Module, ada: nn.Module, vgg: nn.Module, lr: float = 1e-4,
-                 activation: str = "softmax", distributed: Optional[bool] = None, bucket_mb: int = 25):
+                 activation: str = "softmax", distributed: Optional[bool] = None, bucket_mb: int = 25,
+                 attn_precision: str = "fp32"):
         import network
+        if attn_precision not in ("fp32", "bf16"):
+            raise ValueError(f"Trainer: attn_precision must be 'fp32' or 'bf16', got {attn_precision!r}")
+        # "bf16": the MHAda attention core of 8-head (head width 64) softmax models on the bf16-MFMA
+        # training kernels (autograd_path.MHAdaAttnBf16Fn), fp32 tensors throughout; everything else,
+        # and every other model, keeps its fp32 arithmetic.  Applies to this trainer's forward passes.
+        self.attn_precision = attn_precision
         self.vit_c, self.vit_s, self.ada, self.vgg = vit_c, vit_s, ada, vgg
         dev = next(vit_c.parameters()).device
         self.no_learn = nn.ModuleList([  # train_image.py:52-58
@@ -152,10 +160,19 @@ class Trainer:
         for o in (self.opt_vit_c, self.opt_vit_s, self.opt_ada):
             o.zero_grad()
 
+    def _attn_mode(self):
+        """The context of this trainer's forward passes: attn_precision "bf16" selects
+        autograd_path.TRAIN_ATTN = "bf16" for their duration; "fp32" changes nothing."""
+        if self.attn_precision == "bf16":
+            from .autograd_path import train_attn
+            return train_attn("bf16")
+        return contextlib.nullcontext()
+
     def backward(self, content: torch.Tensor, style: torch.Tensor) -> Dict[str, torch.Tensor]:
         """zero_grad + forward + backward + (all-reduce); no optimizer step."""
         self.zero_grad()
-        out = self.losses(content, style)
+        with self._attn_mode():
+            out = self.losses(content, style)
         out["loss"].backward()
         if self.reducer is not None:
             self.reducer.finish()
@@ -298,7 +315,8 @@ class VideoTrainer(Trainer):
     def backward(self, style, c1, c2, flow, mask) -> Dict[str, torch.Tensor]:
         """zero_grad + forward + backward + (all-reduce); no optimizer step."""
         self.zero_grad()
-        out = self.video_losses(style, c1, c2, flow, mask)
+        with self._attn_mode():
+            out = self.video_losses(style, c1, c2, flow, mask)
         out["loss"].backward()
         if self.reducer is not None:
             self.reducer.finish()
