@@ -352,6 +352,22 @@ int mhada_attn_train_bwd_hd(const float* q, const float* k, const float* v, cons
                             const float* dmo, const float* dd, float* dq, float* dk, float* dv,
                             int BH, int D, int Nc, int Ns, mhada_stream_t stream);
 
+/* ---- the dQ half alone (csrc/attn_train.hip, csrc/attn_train_hd.hip) -----------------------------
+ * Added to ABI 18 WITHOUT a version bump, for the reasons given for the _hd entries above: purely
+ * additive, found by symbol.
+ *
+ * The backward of adaDecoder.py:186-198 when only the query side carries a gradient — a feature
+ * inversion (visual_mhada.py:111-127) optimises the content image while the style features come
+ * from a no-grad call and the weights are frozen, so dK and dV' have no consumer.  Each entry
+ * launches only the query-stationary dQ kernel of mhada_attn_train_bwd / mhada_attn_train_bwd_hd
+ * (S and dA recomputed, no workspace) with the same operands and host checks: dq has the bits of
+ * that call's dq; dk, dv are not computed.  mhada_attn_train_dq_hd: D = 32 | 128, Nc == 0 legal
+ * (nothing launched). */
+int mhada_attn_train_dq(const float* q, const float* k, const float* v, const float* lse, const float* dmo,
+                        const float* dd, float* dq, int BH, int Nc, int Ns, mhada_stream_t stream);
+int mhada_attn_train_dq_hd(const float* q, const float* k, const float* v, const float* lse, const float* dmo,
+                           const float* dd, float* dq, int BH, int D, int Nc, int Ns, mhada_stream_t stream);
+
 /* ---- bf16 training attention at head width 64 (csrc/attn_train_bf16.hip) ------------------------
  * Added to ABI 18 WITHOUT a version bump, for the reasons given for the _hd entries above: the
  * three entries are purely additive and are found by symbol.
@@ -637,6 +653,21 @@ int mhada_out3_dgrad(const float* dy, const float* y, const float* wd, const flo
 long long mhada_out3_wgrad_work(int B, int H, int W);
 int mhada_out3_wgrad(const float* x, const float* dy, const float* y, float* dw, float* db, float* work,
                      long long work_floats, int B, int H, int W, mhada_stream_t stream);
+
+/* Input gradient of the ViT's patch embedding (vit.py:105-117: Conv2d(3, C, 8, stride 8)) with respect
+ * to the image (csrc/patch_dgrad.hip) — what a feature inversion through the frozen ViT needs
+ * (visual_vit.py:88-112, visual_mhada.py:111-127; aten: the conv's conv_transpose2d backward).
+ * Added to ABI 18 WITHOUT a version bump (purely additive, found by symbol; see the _hd entries).
+ *   dimg[b][c][8 py + ky][8 px + kx] = sum_n dy[b][py (W/8) + px][n] w[n][64 c + 8 ky + kx]
+ * dy [B][(H/8)(W/8)][C] fp32 token rows; w the conv weight (C, 3, 8, 8) as [C][192] (the k order
+ * of MHADA_A_PATCH8); dimg NCHW [B][3][H][W] fp32, every element written: the H % 8 rows below the
+ * last full patch, which the forward ignores, are written as zeros.  fp32 MFMA, fp32 accumulation
+ * in a fixed order, one writer per pixel, no atomics: repeated calls return the same bits.
+ * Host checks before the launch: a null pointer, B <= 0, Ci != 3, C not a positive multiple of 64,
+ * H < 8, W < 8 or W % 8 != 0, a pointer not 16-byte aligned, dy or dimg of 2^31 elements or more
+ * (32-bit element offsets) return MHADA_ERR_ARG. */
+int mhada_patch_embed_dgrad(const float* dy, const float* w, float* dimg, int B, int C, int Ci, int H, int W,
+                            mhada_stream_t stream);
 
 #ifdef __cplusplus
 }

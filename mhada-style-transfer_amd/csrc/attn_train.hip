@@ -754,6 +754,18 @@ extern "C" int mhada_attn_train_bwd(const float* q, const float* k, const float*
   return check_launch("mhada_attn_train_bwd");
 }
 
+extern "C" int mhada_attn_train_dq(const float* q, const float* k, const float* v, const float* lse, const float* dmo,
+                                   const float* dd, float* dq, int BH, int Nc, int Ns, mhada_stream_t s_) {
+  if (!q || !k || !v || !lse || !dmo || !dd || !dq || BH <= 0 || Nc <= 0 || Ns <= 0)
+    return fail("mhada_attn_train_dq: bad args");
+  TrainP p = {};
+  p.q = q; p.k = k; p.v = v; p.lse = const_cast<float*>(lse); p.dmo = dmo; p.dd = dd; p.dq = dq;
+  p.Nc = Nc; p.Ns = Ns;
+  if (!set_grid(p, BH, Nc)) return fail("mhada_attn_train_dq: grid too large");
+  hipLaunchKernelGGL(attn_train_dq_kernel<kNW>, dim3(p.nblk), dim3(64 * kNW), 0, (hipStream_t)s_, p);
+  return check_launch("mhada_attn_train_dq");
+}
+
 extern "C" int mhada_attn_train_dkv(const float* q, const float* k, const float* v, const float* lse,
                                     const float* dmo, const float* dd, float* dk, float* dv, float* ds, int BH,
                                     int Nc, int Ns, mhada_stream_t s_) {

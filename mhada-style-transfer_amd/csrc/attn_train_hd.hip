@@ -477,3 +477,21 @@ extern "C" int mhada_attn_train_bwd_hd(const float* q, const float* k, const flo
   else hipLaunchKernelGGL((attn_train_dkv_hd_kernel<128, 1>), dim3(p.nblk), dim3(64 * kNW), 0, s, p);
   return check_launch("mhada_attn_train_bwd_hd");
 }
+
+extern "C" int mhada_attn_train_dq_hd(const float* q, const float* k, const float* v, const float* lse,
+                                      const float* dmo, const float* dd, float* dq, int BH, int D, int Nc, int Ns,
+                                      mhada_stream_t s_) {
+  if (!q || !k || !v || !lse || !dmo || !dd || !dq || BH <= 0 || Nc < 0 || Ns <= 0)
+    return fail("mhada_attn_train_dq_hd: bad args");
+  if (!hd_width(D)) return fail("mhada_attn_train_dq_hd: D must be 32 or 128 (64: mhada_attn_train_dq)");
+  if (Nc > kMaxRows || Ns > kMaxRows) return fail("mhada_attn_train_dq_hd: Nc, Ns above 2^30");
+  if (Nc == 0) return MHADA_OK;
+  TrainHdP p = {};
+  p.q = q; p.k = k; p.v = v; p.lse = const_cast<float*>(lse); p.dmo = dmo; p.dd = dd; p.dq = dq;
+  p.Nc = Nc; p.Ns = Ns;
+  if (!set_grid(p, BH, Nc)) return fail("mhada_attn_train_dq_hd: grid too large");
+  const hipStream_t s = (hipStream_t)s_;
+  if (D == 32) hipLaunchKernelGGL((attn_train_dq_hd_kernel<32, 2>), dim3(p.nblk), dim3(64 * kNW), 0, s, p);
+  else hipLaunchKernelGGL((attn_train_dq_hd_kernel<128, 1>), dim3(p.nblk), dim3(64 * kNW), 0, s, p);
+  return check_launch("mhada_attn_train_dq_hd");
+}

@@ -90,6 +90,9 @@ SIGNATURES = {
     "mhada_attn_train_dkv": (_I, [_vp] * 9 + [_I, _I, _I, _vp]),
     "mhada_attn_train_fwd_hd": (_I, [_vp] * 7 + [_I, _I, _I, _I, _vp]),
     "mhada_attn_train_bwd_hd": (_I, [_vp] * 9 + [_I, _I, _I, _I, _vp]),
+    "mhada_attn_train_dq": (_I, [_vp] * 7 + [_I, _I, _I, _vp]),
+    "mhada_attn_train_dq_hd": (_I, [_vp] * 7 + [_I, _I, _I, _I, _vp]),
+    "mhada_patch_embed_dgrad": (_I, [_vp, _vp, _vp, _I, _I, _I, _I, _I, _vp]),
     "mhada_attn_train_bf16_workspace": (_c_ll, [_I, _I, _I, _I]),
     "mhada_attn_train_fwd_bf16": (_I, [_vp] * 8 + [_c_ll, _I, _I, _I, _vp]),
     "mhada_attn_train_bwd_bf16": (_I, [_vp] * 10 + [_c_ll, _I, _I, _I, _I, _vp]),

@@ -40,6 +40,30 @@ def train_attn(mode: str):
     finally:
         TRAIN_ATTN = saved
 
+# An image that requires grad (a feature inversion: visual_vit.py:88-112, visual_mhada.py:111-127)
+# through vit_forward on a ROCm device.  "hip": the HIP training kernels, the image gradient from
+# mhada_patch_embed_dgrad (hidden widths with C % 64 == 0; any other width keeps aten); "torch": the
+# aten modules, forward and backward (A/B, tests).
+VIT_INPUT_GRAD = "hip"
+
+
+@contextlib.contextmanager
+def vit_input_grad(mode: str):
+    """Run the enclosed forward passes with VIT_INPUT_GRAD = ``mode``; restores the previous value."""
+    global VIT_INPUT_GRAD
+    if mode not in ("hip", "torch"):
+        raise ValueError(f"vit_input_grad: mode must be 'hip' or 'torch', got {mode!r}")
+    saved, VIT_INPUT_GRAD = VIT_INPUT_GRAD, mode
+    try:
+        yield
+    finally:
+        VIT_INPUT_GRAD = saved
+
+
+# MHAdaAttnFn.backward when neither k nor v needs a gradient (the style side of an inversion): True
+# = the dQ kernel alone (ops.attn_train_dq / attn_train_dq_hd); False = the full backward (A/B).
+ATTN_DQ_ONLY = True
+
 # decoder layers and whether bilinear x2 follows them (conv.py:78-94)
 DECODER_ORDER = (("conv1", 0, True), ("conv1", 1, False), ("conv1", 2, False), ("conv1", 3, False),
                  ("conv1", 4, True), ("conv2", 0, False), ("conv2", 1, True), ("conv3", 0, False),
@@ -97,15 +121,25 @@ def _vit_forward_hip(vit, x: torch.Tensor, groups: int = 1) -> List[torch.Tensor
     return outs
 
 
+def _image_grad_on_hip(vit, x: torch.Tensor) -> bool:
+    """An image that carries a gradient takes the HIP path when mhada_patch_embed_dgrad accepts the
+    model (3 input channels, hidden width a multiple of 64) and VIT_INPUT_GRAD allows it."""
+    if not x.requires_grad:
+        return True
+    w = vit.patch_embedding.conv_proj.weight
+    return VIT_INPUT_GRAD == "hip" and w.shape[0] % 64 == 0 and w.shape[1] == 3
+
+
 def vit_forward(vit, x: torch.Tensor, groups: int = 1) -> List[torch.Tensor]:
     """VisionTransformer.forward (vit.py:148-169); the MHA keeps batch_first=False on a
     (B, N, C) tensor, i.e. attends over the batch axis exactly as the reference.  On a ROCm
-    device the HIP training kernels run it (_vit_forward_hip); the CPU uses aten.
+    device the HIP training kernels run it (_vit_forward_hip), an image that requires grad included
+    (VIT_INPUT_GRAD); the CPU uses aten.
 
     ``groups`` > 1: x is that many calls' batches concatenated (B = groups x L); the batch-axis
     attention runs over each call's L images separately, everything else is per token, so the
     outputs are those of the separate calls (Trainer.batch_vit)."""
-    if x.is_cuda and vit.patch_size == 8 and not x.requires_grad and \
+    if x.is_cuda and vit.patch_size == 8 and _image_grad_on_hip(vit, x) and \
             isinstance(vit.encoder[0].mlp[1], torch.nn.ReLU) and vit.encoder[0].attention.in_proj_weight is not None:
         return _vit_forward_hip(vit, x, groups)
     if groups > 1:
@@ -144,7 +178,8 @@ class MHAdaAttnFn(torch.autograd.Function):
     (csrc/attn_train.hip; head widths 32 and 128: csrc/attn_train_hd.hip):
     out' = sqrt(max(E2' - M'^2, 1e-6)) * x + M' with M' = A V', E2' = A V'^2, A = softmax(q k^T).
     q, x (BH, Nc, D); k, v (BH, Ns, D), v centred, D = 64 | 32 | 128.
-    A is never stored: the backward recomputes it from the saved row normaliser."""
+    A is never stored: the backward recomputes it from the saved row normaliser.  When neither k nor
+    v needs a gradient the backward runs the dQ kernel alone (ATTN_DQ_ONLY)."""
 
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
@@ -161,12 +196,22 @@ class MHAdaAttnFn(torch.autograd.Function):
         q, k, v, x, mo, lse = ctx.saved_tensors
         # S = sqrt(max(E2' - M'^2, 1e-6)), out' = S x + M': dx = dout S, dVar = dout x / (2 S) where
         # the clamp is inactive, dM' = dout - 2 M' dVar, dd = rowsum(dM' M' + dVar E2')  (one kernel)
+        # neither k nor v needs a gradient (an inversion's no-grad style features and frozen weights):
+        # the dQ kernel alone
+        dq_only = ATTN_DQ_ONLY and not ctx.needs_input_grad[1] and not ctx.needs_input_grad[2]
+        dk = dv = None
         if q.shape[-1] == 64:
             dx, dmo, dd = ops.attn_train_bwd_prep(dout.contiguous(), x, mo)
-            dq, dk, dv = ops.attn_train_bwd(q, k, v, lse, dmo, dd)
+            if dq_only:
+                dq = ops.attn_train_dq(q, k, v, lse, dmo, dd)
+            else:
+                dq, dk, dv = ops.attn_train_bwd(q, k, v, lse, dmo, dd)
         else:
             dx, dmo, dd = ops.attn_train_bwd_prep_hd(dout.contiguous(), x, mo)
-            dq, dk, dv = ops.attn_train_bwd_hd(q, k, v, lse, dmo, dd)
+            if dq_only:
+                dq = ops.attn_train_dq_hd(q, k, v, lse, dmo, dd)
+            else:
+                dq, dk, dv = ops.attn_train_bwd_hd(q, k, v, lse, dmo, dd)
         return dq, dk, dv, dx
 
 

@@ -147,6 +147,33 @@ def patch_embed(img: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, pos: Opt
                 r=pos, ldr=C, sr=(0, 0), ldc=C, sc=(N * C, 0))
 
 
+def patch_embed_dgrad(dy: torch.Tensor, w: torch.Tensor, H: int, W: int,
+                      out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``mhada_patch_embed_dgrad``: the image gradient of the 8x8 / stride-8 patch embedding.  dy
+    [B][(H//8)(W//8)][C] fp32 token rows, w the conv weight (C, Ci, 8, 8) or its [C][64 Ci] view ->
+    (B, Ci, H, W) fp32.  The kernel writes every element (zeros in the H % 8 rows the forward
+    ignores); ``out``: a contiguous fp32 (B, Ci, H, W) buffer to write into."""
+    _need_gpu(dy, w, out)
+    for t, what in ((dy, "dy"), (w, "w"), (out, "out")):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
+            raise ValueError(f"patch_embed_dgrad: {what} must be contiguous float32")
+    if dy.dim() != 3 or w.dim() not in (2, 4) or w.shape[0] != dy.shape[2] or (w.dim() == 4 and w.shape[2:] != (8, 8)) \
+            or (w.dim() == 2 and w.shape[1] % 64):
+        raise ValueError(f"patch_embed_dgrad: dy [B][N][C] and w (C, Ci, 8, 8) or [C][64 Ci], got "
+                         f"{tuple(dy.shape)} and {tuple(w.shape)}")
+    B, N, C = dy.shape
+    Ci = w.shape[1] if w.dim() == 4 else w.shape[1] // 64
+    if H < 8 or W < 8 or N != (H // 8) * (W // 8):
+        raise ValueError(f"patch_embed_dgrad: {N} token rows do not match a {H} x {W} image")
+    if out is None:
+        # H % 8 rows below the last patch: zeros (the kernel writes them too, for a caller's ``out``)
+        out =(torch.zeros if H % 8 else torch.empty)(B, Ci, H, W, device=dy.device, dtype=torch.float32)
+    elif out.shape != (B, Ci, H, W):
+        raise ValueError(f"patch_embed_dgrad: out must be {(B, Ci, H, W)}, got {tuple(out.shape)}")
+    _call("mhada_patch_embed_dgrad", dy, dy.data_ptr(), w.data_ptr(), out.data_ptr(), B, C, Ci, H, W)
+    return out
+
+
 # fp32 3x3 convs run as Winograd F(2x2,3x3) (csrc/wino.hip) where the shape allows it; False
 # forces the implicit-GEMM direct product (A/B measurements, tests).
 WINO = True
@@ -890,6 +917,27 @@ def attn_train_bwd(q, k, v, lse, dmo, dd, spill: Optional[bool] = None):
     return dq, dk, dv
 
 
+# Calls of the dQ-only backward (attn_train_dq / attn_train_dq_hd), counted apart from BWD_PATH_COUNTS.
+DQ_ONLY_COUNTS = {"dq_only": 0}
+
+
+def attn_train_dq(q, k, v, lse, dmo, dd):
+    """``mhada_attn_train_dq``: the dq (BH, Nc, 64) of ``attn_train_bwd(..., spill=False)`` alone — the
+    query-stationary recompute kernel, bit-identical to that call's dq; dk and dv are not computed
+    (a feature inversion: the key / value side carries no gradient)."""
+    _rows64(q, k, v, lse, dmo, dd)
+    BH, Nc, _ = q.shape
+    Ns = k.shape[1]
+    if lse.shape != (BH, Nc) or dmo.shape != (BH, Nc, 128) or dd.shape != (BH, Nc) or k.shape != (BH, Ns, 64) \
+            or v.shape != k.shape:
+        raise ValueError("attn_train_dq: bad shapes")
+    DQ_ONLY_COUNTS["dq_only"] += 1
+    dq = torch.empty_like(q)
+    _call("mhada_attn_train_dq", q, q.data_ptr(), k.data_ptr(), v.data_ptr(), lse.data_ptr(), dmo.data_ptr(),
+          dd.data_ptr(), dq.data_ptr(), BH, Nc, Ns)
+    return dq
+
+
 def _train_hd_width(what: str, t: torch.Tensor) -> int:
     D = t.shape[-1] if t.dim() == 3 else -1
     if D not in (32, 128):
@@ -933,6 +981,23 @@ def attn_train_bwd_hd(q, k, v, lse, dmo, dd):
     _call("mhada_attn_train_bwd_hd", q, q.data_ptr(), k.data_ptr(), v.data_ptr(), lse.data_ptr(), dmo.data_ptr(),
           dd.data_ptr(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), BH, D, Nc, Ns)
     return dq, dk, dv
+
+
+def attn_train_dq_hd(q, k, v, lse, dmo, dd):
+    """``mhada_attn_train_dq_hd``: ``attn_train_dq`` at head width D = 32 | 128 — the dq of
+    ``attn_train_bwd_hd`` alone, bit-identical to it."""
+    _rows64(q, k, v, lse, dmo, dd)
+    D = _train_hd_width("attn_train_dq_hd", q)
+    BH, Nc, _ = q.shape
+    Ns = k.shape[1] if k.dim() == 3 else -1
+    if lse.shape != (BH, Nc) or dmo.shape != (BH, Nc, 2 * D) or dd.shape != (BH, Nc) or k.shape != (BH, Ns, D) \
+            or v.shape != k.shape or Ns <= 0:
+        raise ValueError("attn_train_dq_hd: bad shapes")
+    DQ_ONLY_COUNTS["dq_only"] += 1
+    dq = torch.empty_like(q)
+    _call("mhada_attn_train_dq_hd", q, q.data_ptr(), k.data_ptr(), v.data_ptr(), lse.data_ptr(), dmo.data_ptr(),
+          dd.data_ptr(), dq.data_ptr(), BH, D, Nc, Ns)
+    return dq
 
 
 # Calls of the bf16 training attention (attn_train_fwd_bf16 / attn_train_bwd_bf16): tests and tools

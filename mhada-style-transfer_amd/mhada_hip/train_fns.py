@@ -15,7 +15,8 @@ the reference, and runs its forward and backward through libmhada_hip.so:
   adaDecoder.py:152,205), optional fused ReLU: forward mhada_gemm; backward dX = dY W (mhada_gemm
   with W^T), dW = dY^T X and db = colsum(dY) in one mhada_gemm_tn pass.
 * ``patch_embed`` — the 8x8 / stride-8 patch conv (vit.py:105-117): forward mhada_gemm PATCH8,
-  weight gradient mhada_gemm_tn PATCH8 (the input image needs no gradient in training).
+  weight gradient mhada_gemm_tn PATCH8, image gradient (feature inversion; training images are
+  data and need none) mhada_patch_embed_dgrad.
 * ``maxpool2``, ``upsample2x`` (conv.py:71), ``vgg_input`` (vgg19.py:6-12) and their adjoints.
 """
 from __future__ import annotations
@@ -455,7 +456,9 @@ class BatchAxisAttnFn(torch.autograd.Function):
 
 class PatchEmbedFn(torch.autograd.Function):
     """PatchEmbedding conv 8x8 / stride 8 (vit.py:105-117): img (B, 3, H, W) fp32 -> tokens
-    [B][N][C]; weight (C, 3, 8, 8).  Gradients for the weight and bias only."""
+    [B][N][C]; weight (C, 3, 8, 8).  Backward: the weight gradient on mhada_gemm_tn PATCH8 (bias: its
+    column sums), skipped for frozen parameters; the image gradient, when the image requires grad (a
+    feature inversion), on mhada_patch_embed_dgrad."""
 
     @staticmethod
     def forward(ctx, img, weight, bias):
@@ -468,12 +471,12 @@ class PatchEmbedFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gy):
         img, weight = ctx.saved_tensors
-        if ctx.needs_input_grad[0]:
-            raise NotImplementedError("PatchEmbedFn: no input-image gradient (training inputs are data)")
         B, Ci, H, W = img.shape
         C = weight.shape[0]
         g = gy.contiguous().view(-1, C)
-        gw = gb = None
+        gx = gw = gb = None
+        if ctx.needs_input_grad[0]:
+            gx = ops.patch_embed_dgrad(g.view(B, -1, C), weight.detach().float().contiguous(), H, W)
         if ctx.needs_input_grad[1]:
             gw, cs = ops.gemm_tn(g, img, M=C, N=64 * Ci, K=g.shape[0], lda=C, b_mode=A_PATCH8, img=(Ci, H, W),
                                  colsum=True)
@@ -482,7 +485,7 @@ class PatchEmbedFn(torch.autograd.Function):
                 gb = cs
         elif ctx.needs_input_grad[2]:
             gb = ops.colsum(g)
-        return None, gw, gb
+        return gx, gw, gb
 
 
 class MaxPool2Fn(torch.autograd.Function):
