@@ -330,7 +330,7 @@ int mhada_attn_train_dkv(const float* q, const float* k, const float* v, const f
                          const float* dd, float* dk, float* dv, float* ds, int BH, int Nc, int Ns,
                          mhada_stream_t stream);
 
-/* ---- training at head widths D = 32 | 128 (csrc/attn_train_hd.hip) ----------------------------
+/* ---- training at head widths D = 32 | 128 (csrc/attn_train.hip) -------------------------------
  * Added to ABI 18 WITHOUT a version bump: the three entries below are purely additive (no existing
  * signature, struct or knob changes), ABI 18 is the version that introduced the D-wide entry points
  * they complete, and the binding checks the version for equality — a caller built against the
@@ -352,7 +352,7 @@ int mhada_attn_train_bwd_hd(const float* q, const float* k, const float* v, cons
                             const float* dmo, const float* dd, float* dq, float* dk, float* dv,
                             int BH, int D, int Nc, int Ns, mhada_stream_t stream);
 
-/* ---- the dQ half alone (csrc/attn_train.hip, csrc/attn_train_hd.hip) -----------------------------
+/* ---- the dQ half alone (csrc/attn_train.hip) ---------------------------------------------------
  * Added to ABI 18 WITHOUT a version bump, for the reasons given for the _hd entries above: purely
  * additive, found by symbol.
  *

@@ -1,26 +1,45 @@
-// MHAda attention for the training path: forward that keeps the softmax statistics, and the
-// backward (dual accumulator M / E2), fp32 on v_mfma_f32_32x32x2_f32.
+// MHAda attention for the training path at head widths D = 32 | 64 | 128 (16-, 8- and 4-head models
+// at 512 channels): forward that keeps the softmax statistics, and the backward (dual accumulator
+// M / E2), one kernel family templated on D, fp32 on v_mfma_f32_32x32x2_f32.
 //
 // Reference: AdaAttnMultiHead.forward (MHAdaSTr/network/adaDecoder.py:186-198) under
-// train_image.py:93-144 autograd.  Per (batch, head), with Q [Nc][64], K [Ns][64], V' [Ns][64]
+// train_image.py:93-144 autograd.  Per (batch, head), with Q [Nc][D], K [Ns][D], V' [Ns][D]
 // (V' = V - mean_tokens(V), centred by the caller under autograd: the variance is
 // shift-invariant and d(out)/dV = d(out)/dV' exactly, since the rows of A sum to one) and
-// X = InstanceNorm(fcs) [Nc][64]:
+// X = InstanceNorm(fcs) [Nc][D]:
 //   A = softmax(Q K^T)   M' = A V'   E2' = A V'^2   var = E2' - M'^2
 //   out' = sqrt(max(var, 1e-6)) * X + M'            (the caller adds mean(V) back)
-// The forward writes out', [M' | E2'] and the log2 row normaliser lse2 = max + log2(sum).
-// The caller turns d(out') into dO = [dM' | dE2'] and D = dM'.M' + dE2'.E2' (elementwise,
-// O(Nc*64)); then with P = A (recomputed from lse2) and dA = dM'.V'^T + dE2'.(V'^2)^T:
-//   dS = P * (dA - D)            (gradient of the natural-unit logits)
+// (no 1/sqrt(d) factor).  The forward writes out', mo = [M' | E2'] ([Nc][2D]) and the log2 row
+// normaliser lse2 = max + log2(sum).
+// The caller turns d(out') into dmo = [dM' | dE2'] and D_row = dM'.M' + dE2'.E2' (elementwise,
+// O(Nc*D): mhada_attn_train_bwd_prep / _hd); then with P = A (recomputed from lse2) and
+// dA = dM'.V'^T + dE2'.(V'^2)^T:
+//   dS = P * (dA - D_row)        (gradient of the natural-unit logits)
 //   dQ = dS K       dK = dS^T Q       dV' = P^T dM' + 2 V' * (P^T dE2')
 // as two deterministic kernels (no atomics): key-stationary dK/dV', query-stationary dQ, each
 // recomputing P — the Nc x Ns matrices never reach HBM (the reference autograd keeps A, the
 // softmax output, and their gradients: 4 B x Nc x Ns per head each).
 //
+// The kernels stage 32-row LDS tiles through registers (two buffers, one barrier per tile).  At
+// 64 only, the dK/dV' kernel can also spill dS (dQ = dS K then runs as a GEMM), in this form or in
+// the LDS-DMA form below (the training default); the SPLIT3 and vt forwards (attn_split3.hip,
+// attn.hip) exist at 64 only too.
+//
 // MFMA 32x32x2 f32 layout (cdna_hip_programming.md §3): lane l gives A[l%32][l/32] and
 // B[l/32][l%32]; accumulator register r of lane l is D[acc_row(r, l/32)][l%32].  Every
 // product is arranged so that one operand is an accumulator of the previous product
-// (accumulator-as-operand), so no score or probability ever moves between lanes.
+// (accumulator-as-operand), so no score or probability ever moves between lanes.  A product over
+// D k-indices is D/2 instructions: lane half h supplies the indices (D/2) h + s.
+//
+// Registers and LDS per workgroup of 4 waves (128 queries or keys); DESIGN.md §3b has the
+// compiler's figures:
+//   D = 32:  two waves per SIMD everywhere (accumulators: fwd 2 blocks, dQ 1, dK/dV' 3).
+//   D = 64:  fwd and dQ two waves per SIMD; dK/dV' one: 288 registers, no spills (two waves per
+//            SIMD at 256 registers spilled 18 and measured the same, tools/train_attn_bench.py).
+//   D = 128: one wave per SIMD.  fwd: 8 accumulator blocks (128 registers) + the query row (64);
+//            dQ: Q, dM', dE2' rows (192) + 4 blocks; dK/dV': K, V' rows (128; V'^2 is squared at
+//            the operand, not kept) + dK, P^T dM', P^T dE2' (12 blocks, 192 registers); its Q
+//            (16.5 KiB) and dmo (32.5 KiB) tiles double-buffered take 98 KiB of LDS.
 #include "common.h"
 
 #include <type_traits>
@@ -32,8 +51,15 @@ namespace {
 
 constexpr float kLog2e = 1.4426950408889634f;
 constexpr int TT = 32;    // keys (fwd, dQ) or queries (dK/dV') staged per LDS tile
-constexpr int LP = 68;    // padded LDS row of 64 floats
-constexpr int LPO = 132;  // padded LDS row of 128 floats
+constexpr int kNT = 256;  // threads per workgroup: 4 waves of 32 lane columns, so
+constexpr int kRowsWG = 128;  // queries (fwd, dQ) or keys (dK/dV') per workgroup
+
+// The per-width decisions.  Minimum waves per SIMD handed to the register allocator (the second
+// launch bound; 0 = none given, the 64-wide forward and dQ):
+enum Kind { FWD, DQ, DKV };
+constexpr int min_waves(int D, Kind kind) { return D == 32 ? 2 : D == 128 ? 1 : kind == DKV ? 1 : 0; }
+// dK/dV': V'^2 of the wave's keys kept in registers, or (the budget at 128) squared at the operand
+constexpr bool keep_v2(int D) { return D <= 64; }
 
 MHADA_DEV int acc_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
 
@@ -44,19 +70,19 @@ MHADA_DEV f32x16 mfma(float a, float b, const f32x16& c) {
 }
 
 struct TrainP {
-  const float* q;    // [BH][Nc][64]
-  const float* k;    // [BH][Ns][64]
-  const float* v;    // [BH][Ns][64] centred V'
-  const float* x;    // [BH][Nc][64] InstanceNorm(fcs)
-  float* out;        // [BH][Nc][64]
-  float* mo;         // [BH][Nc][128]  M' | E2'
-  float* lse;        // [BH][Nc]       log2 units
-  const float* dmo;  // [BH][Nc][128]  dM' | dE2'
-  const float* dd;   // [BH][Nc]       D
-  float* dq;         // [BH][Nc][64]
-  float* dk;         // [BH][Ns][64]
-  float* dv;         // [BH][Ns][64]
-  float* ds;         // [BH][Nc][Ns] dS spill (dQ = dS K as a GEMM), or null
+  const float* q;    // [BH][Nc][D]
+  const float* k;    // [BH][Ns][D]
+  const float* v;    // [BH][Ns][D] centred V'
+  const float* x;    // [BH][Nc][D] InstanceNorm(fcs)
+  float* out;        // [BH][Nc][D]
+  float* mo;         // [BH][Nc][2D]  M' | E2'
+  float* lse;        // [BH][Nc]      log2 units
+  const float* dmo;  // [BH][Nc][2D]  dM' | dE2'
+  const float* dd;   // [BH][Nc]      D_row
+  float* dq;         // [BH][Nc][D]
+  float* dk;         // [BH][Ns][D]
+  float* dv;         // [BH][Ns][D]
+  float* ds;         // [BH][Nc][Ns] dS spill (dQ = dS K as a GEMM; D = 64), or null
   int Nc, Ns, nb, nblk;  // nb = row blocks per (b, h)
 };
 
@@ -92,13 +118,16 @@ MHADA_DEV void lds_barrier() {
 }
 
 // Register-staged copy of rows [r0, r0+TT) of a [n][W] matrix (zero rows past n; with CLAMP, r0
-// may lie past n) into a padded LDS tile: load() issues the global reads one tile ahead, store()
-// writes them after the current tile's math (one barrier per tile, two LDS buffers).
-template <int NT, int W, bool CLAMP = false>
+// may lie past n) into an LDS tile of rows padded to W + 4 floats (row reads by ds_read_b128 and
+// column reads by ds_read_b32 are both conflict-free: W + 4 = 4 mod 32): load() issues the global
+// reads one tile ahead, store() writes them after the current tile's math (one barrier per tile,
+// two LDS buffers).  Row offsets are 64-bit.
+template <int W, bool CLAMP = false>
 struct Stager {
-  static constexpr int CPR = W / 4;             // 16-B chunks per row
-  static constexpr int N = TT * CPR / NT;       // chunks per thread
-  static constexpr int LD = W == 64 ? LP : LPO;
+  static constexpr int NT = kNT;
+  static constexpr int CPR = W / 4;        // 16-B chunks per row
+  static constexpr int N = TT * CPR / NT;  // chunks per thread
+  static constexpr int LD = W + 4;
   static_assert(N * NT == TT * CPR, "tile must divide evenly");
   f32x4 r[N];
   MHADA_DEV void load(const float* g, int r0, int n, int tid) {
@@ -124,11 +153,12 @@ struct Stager {
   }
 };
 
-// Per-lane row of 64 floats split by lane half: reg[s] = g[row][32h + s] * scale.
-MHADA_DEV void load_half_row(float (&reg)[32], const float* g, int row, bool valid, int h, float scale) {
-  const float* p = g + (long long)(valid ? row : 0) * 64 + 32 * h;
+// The lane's half of a row of D = 2 HD floats: reg[s] = g[row][HD h + s] * scale (zeros if !valid).
+template <int HD>
+MHADA_DEV void load_half_row(float (&reg)[HD], const float* g, int row, bool valid, int h, float scale) {
+  const float* p = g + (long long)(valid ? row : 0) * (2 * HD) + HD * h;
 #pragma unroll
-  for (int i = 0; i < 8; ++i) {
+  for (int i = 0; i < HD / 4; ++i) {
     const f32x4 t = ld4(p + 4 * i);
 #pragma unroll
     for (int e = 0; e < 4; ++e) reg[4 * i + e] = valid ? t[e] * scale : 0.f;
@@ -137,11 +167,12 @@ MHADA_DEV void load_half_row(float (&reg)[32], const float* g, int row, bool val
 
 // S^T (keys x queries) in log2 units from the staged K tile and the lane's query row
 // (qr pre-scaled by log2 e); keys past Ns masked to -inf.
-MHADA_DEV f32x16 scores_t(const float* sK, const float (&qr)[32], int k0, int Ns, int h, int r32) {
+template <int HD>
+MHADA_DEV f32x16 scores_t(const float* sK, const float (&qr)[HD], int k0, int Ns, int h, int r32) {
   f32x16 S = {};
-  const float* kr = sK + r32 * LP + 32 * h;
+  const float* kr = sK + r32 * (2 * HD + 4) + HD * h;
 #pragma unroll
-  for (int i = 0; i < 8; ++i) {
+  for (int i = 0; i < HD / 4; ++i) {
     const f32x4 kk = ld4(kr + 4 * i);
 #pragma unroll
     for (int e = 0; e < 4; ++e) S = mfma(kk[e], qr[4 * i + e], S);
@@ -154,29 +185,61 @@ MHADA_DEV f32x16 scores_t(const float* sK, const float (&qr)[32], int k0, int Ns
   return S;
 }
 
+// accumulator blocks b = 0 .. DB-1 of a lane hold columns 32 b + 8 g + 4 h + e in register 4 g + e
+template <int DB>
+MHADA_DEV void store_blocks(float* row, const f32x16 (&A)[DB], int h) {
+#pragma unroll
+  for (int b = 0; b < DB; ++b)
+#pragma unroll
+    for (int g = 0; g < 4; ++g)
+      st4(row + 32 * b + 8 * g + 4 * h, f32x4{A[b][4 * g], A[b][4 * g + 1], A[b][4 * g + 2], A[b][4 * g + 3]});
+}
+
+// dK/dV' epilogue of the lane's key row (vg, dvr, dkr: its rows of V', dV', dK):
+// dV' = G1 + 2 V' G2 with G1 = P^T dM', G2 = P^T dE2'.
+template <int DB>
+MHADA_DEV void store_dkv(const float* vg, float* dvr, float* dkr, int h, const f32x16 (&G1)[DB],
+                         const f32x16 (&G2)[DB], const f32x16 (&dK)[DB]) {
+#pragma unroll
+  for (int cb = 0; cb < DB; ++cb)
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const int c0 = 32 * cb + 8 * g + 4 * h;
+      const f32x4 vv = ld4(vg + c0);
+      f32x4 a, b;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        a[e] = G1[cb][4 * g + e] + 2.0f * vv[e] * G2[cb][4 * g + e];
+        b[e] = dK[cb][4 * g + e];
+      }
+      st4(dvr + c0, a);
+      st4(dkr + c0, b);
+    }
+}
+
 // ---------------------------------------------------------------------------------------
 // forward: wave = 32 queries (one per lane column), online softmax over 32-key tiles
 // ---------------------------------------------------------------------------------------
-template <int NW>
-__global__ void __launch_bounds__(64 * NW) attn_train_fwd_kernel(const TrainP p) {
-  constexpr int NT = 64 * NW;
-  __shared__ __attribute__((aligned(16))) float sK[2][TT * LP];
-  __shared__ __attribute__((aligned(16))) float sV[2][TT * LP];
-  const int t = xcd_remap(blockIdx.x, p.nblk);
-  const long long bh = t / p.nb;
+template <int D>
+__global__ void __launch_bounds__(kNT, min_waves(D, FWD)) attn_train_fwd_kernel(const TrainP p) {
+  constexpr int DB = D / 32, LD = D + 4;
+  __shared__ __attribute__((aligned(16))) float sK[2][TT * LD];
+  __shared__ __attribute__((aligned(16))) float sV[2][TT * LD];
+  const int t0 = xcd_remap(blockIdx.x, p.nblk);
+  const long long bh = t0 / p.nb;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5, r32 = lane & 31;
-  const int q = (t % p.nb) * 32 * NW + wave * 32 + r32;
+  const int q = (t0 % p.nb) * kRowsWG + wave * 32 + r32;
   const bool qv = q < p.Nc;
-  float qr[32];
-  load_half_row(qr, p.q + bh * p.Nc * 64, q, qv, h, kLog2e);
-  const float* kb = p.k + bh * p.Ns * 64;
-  const float* vb = p.v + bh * p.Ns * 64;
+  float qr[D / 2];
+  load_half_row(qr, p.q + bh * p.Nc * D, q, qv, h, kLog2e);
+  const float* kb = p.k + bh * p.Ns * D;
+  const float* vb = p.v + bh * p.Ns * D;
 
-  f32x16 O[4];
+  f32x16 O[2 * DB];  // blocks 0 .. DB-1: sum p v', DB .. 2 DB-1: sum p v'^2
 #pragma unroll
-  for (int i = 0; i < 4; ++i) O[i] = f32x16{};
+  for (int i = 0; i < 2 * DB; ++i) O[i] = f32x16{};
   float m = -INFINITY, l = 0.f;
-  Stager<NT, 64> gk, gv;
+  Stager<D> gk, gv;
   gk.load(kb, 0, p.Ns, tid);
   gv.load(vb, 0, p.Ns, tid);
   gk.store(sK[0], tid);
@@ -200,7 +263,7 @@ __global__ void __launch_bounds__(64 * NW) attn_train_fwd_kernel(const TrainP p)
       const float alpha = __builtin_amdgcn_exp2f(m - mn);
       l *= alpha;
 #pragma unroll
-      for (int i = 0; i < 4; ++i)
+      for (int i = 0; i < 2 * DB; ++i)
 #pragma unroll
         for (int e = 0; e < 16; ++e) O[i][e] *= alpha;
       m = mn;
@@ -210,15 +273,16 @@ __global__ void __launch_bounds__(64 * NW) attn_train_fwd_kernel(const TrainP p)
       S[r] = __builtin_amdgcn_exp2f(S[r] - m);
       l += S[r];
     }
-    // O^T (c x queries) += V'^T (c x keys) . P^T (keys x queries); blocks 2,3 take V'^2
+    // O^T (c x queries) += V'^T (c x keys) . P^T (keys x queries); the upper blocks take V'^2
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const float* vr = sV[cb] + acc_row(r, h) * LP + r32;
-      const float v0 = vr[0], v1 = vr[32];
-      O[0] = mfma(v0, S[r], O[0]);
-      O[1] = mfma(v1, S[r], O[1]);
-      O[2] = mfma(v0 * v0, S[r], O[2]);
-      O[3] = mfma(v1 * v1, S[r], O[3]);
+      const float* vr = sV[cb] + acc_row(r, h) * LD + r32;
+#pragma unroll
+      for (int b = 0; b < DB; ++b) {
+        const float vv = vr[32 * b];
+        O[b] = mfma(vv, S[r], O[b]);
+        O[DB + b] = mfma(vv * vv, S[r], O[DB + b]);
+      }
     }
     if (nxt) {
       gk.store(sK[cb ^ 1], tid);
@@ -230,27 +294,27 @@ __global__ void __launch_bounds__(64 * NW) attn_train_fwd_kernel(const TrainP p)
   if (!qv) return;
   const float inv = 1.0f / l;
   const long long row = bh * p.Nc + q;
-  const float* xr = p.x + row * 64;
-  float* orow = p.out + row * 64;
-  float* mrow = p.mo + row * 128;
+  const float* xr = p.x + row * D;
+  float* orow = p.out + row * D;
+  float* mrow = p.mo + row * 2 * D;
 #pragma unroll
-  for (int cb = 0; cb < 2; ++cb)
+  for (int b = 0; b < DB; ++b)
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
-      const int c0 = 32 * cb + 8 * g + 4 * h;
+      const int c0 = 32 * b + 8 * g + 4 * h;
       const f32x4 xx = ld4(xr + c0);
       f32x4 o, mm, ee;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        const float m1 = O[cb][4 * g + e] * inv;
-        const float e2 = O[cb + 2][4 * g + e] * inv;
+        const float m1 = O[b][4 * g + e] * inv;
+        const float e2 = O[DB + b][4 * g + e] * inv;
         o[e] = sqrtf(fmaxf(e2 - m1 * m1, 1e-6f)) * xx[e] + m1;
         mm[e] = m1;
         ee[e] = e2;
       }
       st4(orow + c0, o);
       st4(mrow + c0, mm);
-      st4(mrow + 64 + c0, ee);
+      st4(mrow + D + c0, ee);
     }
   if (h == 0) p.lse[row] = m + __log2f(l);
 }
@@ -258,37 +322,29 @@ __global__ void __launch_bounds__(64 * NW) attn_train_fwd_kernel(const TrainP p)
 // ---------------------------------------------------------------------------------------
 // dQ: wave = 32 queries; streams 32-key tiles of K, V'
 // ---------------------------------------------------------------------------------------
-template <int NW>
-__global__ void __launch_bounds__(64 * NW) attn_train_dq_kernel(const TrainP p) {
-  constexpr int NT = 64 * NW;
-  __shared__ __attribute__((aligned(16))) float sK[2][TT * LP];
-  __shared__ __attribute__((aligned(16))) float sV[2][TT * LP];
-  const int t = xcd_remap(blockIdx.x, p.nblk);
-  const long long bh = t / p.nb;
+template <int D>
+__global__ void __launch_bounds__(kNT, min_waves(D, DQ)) attn_train_dq_kernel(const TrainP p) {
+  constexpr int DB = D / 32, HD = D / 2, LD = D + 4;
+  __shared__ __attribute__((aligned(16))) float sK[2][TT * LD];
+  __shared__ __attribute__((aligned(16))) float sV[2][TT * LD];
+  const int t0 = xcd_remap(blockIdx.x, p.nblk);
+  const long long bh = t0 / p.nb;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5, r32 = lane & 31;
-  const int q = (t % p.nb) * 32 * NW + wave * 32 + r32;
+  const int q = (t0 % p.nb) * kRowsWG + wave * 32 + r32;
   const bool qv = q < p.Nc;
   const long long row = bh * p.Nc + (qv ? q : 0);
-  float qr[32], dm[32], de[32];
-  load_half_row(qr, p.q + bh * p.Nc * 64, q, qv, h, kLog2e);
-  {
-    const float* o = p.dmo + row * 128 + 32 * h;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const f32x4 a = ld4(o + 4 * i), b = ld4(o + 64 + 4 * i);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        dm[4 * i + e] = qv ? a[e] : 0.f;
-        de[4 * i + e] = qv ? b[e] : 0.f;
-      }
-    }
-  }
+  float qr[HD], dm[HD], de[HD];
+  load_half_row(qr, p.q + bh * p.Nc * D, q, qv, h, kLog2e);
+  load_half_row(dm, p.dmo + bh * p.Nc * 2 * D, 2 * q, qv, h, 1.0f);      // row q of [Nc][2D], first half
+  load_half_row(de, p.dmo + bh * p.Nc * 2 * D + D, 2 * q, qv, h, 1.0f);  // second half
   const float L = qv ? p.lse[row] : INFINITY;  // invalid query: P = 0
-  const float D = qv ? p.dd[row] : 0.f;
-  const float* kb = p.k + bh * p.Ns * 64;
-  const float* vb = p.v + bh * p.Ns * 64;
-  f32x16 dQ[2] = {f32x16{}, f32x16{}};
-  Stager<NT, 64> gk, gv;
+  const float Dr = qv ? p.dd[row] : 0.f;
+  const float* kb = p.k + bh * p.Ns * D;
+  const float* vb = p.v + bh * p.Ns * D;
+  f32x16 dQ[DB];
+#pragma unroll
+  for (int i = 0; i < DB; ++i) dQ[i] = f32x16{};
+  Stager<D> gk, gv;
   gk.load(kb, 0, p.Ns, tid);
   gv.load(vb, 0, p.Ns, tid);
   gk.store(sK[0], tid);
@@ -303,11 +359,11 @@ __global__ void __launch_bounds__(64 * NW) attn_train_dq_kernel(const TrainP p) 
       gv.load(vb, k0 + TT, p.Ns, tid);
     }
     const f32x16 S = scores_t(sK[cb], qr, k0, p.Ns, h, r32);
-    // dA^T (keys x queries) = [V' | V'^2] (keys x 128) . [dM' | dE2']^T
+    // dA^T (keys x queries) = [V' | V'^2] (keys x 2D) . [dM' | dE2']^T
     f32x16 dA = {};
-    const float* vr = sV[cb] + r32 * LP + 32 * h;
+    const float* vr = sV[cb] + r32 * LD + HD * h;
 #pragma unroll
-    for (int i = 0; i < 8; ++i) {
+    for (int i = 0; i < HD / 4; ++i) {
       const f32x4 vv = ld4(vr + 4 * i);
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
@@ -317,13 +373,13 @@ __global__ void __launch_bounds__(64 * NW) attn_train_dq_kernel(const TrainP p) 
     }
     f32x16 dS;
 #pragma unroll
-    for (int r = 0; r < 16; ++r) dS[r] = __builtin_amdgcn_exp2f(S[r] - L) * (dA[r] - D);
+    for (int r = 0; r < 16; ++r) dS[r] = __builtin_amdgcn_exp2f(S[r] - L) * (dA[r] - Dr);
     // dQ^T (d x queries) += K^T (d x keys) . dS^T (keys x queries)
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const float* kr = sK[cb] + acc_row(r, h) * LP + r32;
-      dQ[0] = mfma(kr[0], dS[r], dQ[0]);
-      dQ[1] = mfma(kr[32], dS[r], dQ[1]);
+      const float* kr = sK[cb] + acc_row(r, h) * LD + r32;
+#pragma unroll
+      for (int b = 0; b < DB; ++b) dQ[b] = mfma(kr[32 * b], dS[r], dQ[b]);
     }
     if (nxt) {
       gk.store(sK[cb ^ 1], tid);
@@ -332,40 +388,46 @@ __global__ void __launch_bounds__(64 * NW) attn_train_dq_kernel(const TrainP p) 
     __syncthreads();
   }
   if (!qv) return;
-  float* o = p.dq + row * 64;
-#pragma unroll
-  for (int db = 0; db < 2; ++db)
-#pragma unroll
-    for (int g = 0; g < 4; ++g)
-      st4(o + 32 * db + 8 * g + 4 * h, f32x4{dQ[db][4 * g], dQ[db][4 * g + 1], dQ[db][4 * g + 2], dQ[db][4 * g + 3]});
+  store_blocks(p.dq + row * D, dQ, h);
 }
 
 // ---------------------------------------------------------------------------------------
-// dK, dV': wave = 32 keys (one per lane column); streams 32-query tiles of Q, dO, lse2, D
+// dK, dV': wave = 32 keys (one per lane column); streams 32-query tiles of Q, dmo, lse2, D_row.
+// SPILL (D = 64): also writes dS [Nc][Ns] for dQ = dS K as a GEMM.
 // ---------------------------------------------------------------------------------------
-template <int NW, int OCC, bool SPILL>
-__global__ void __launch_bounds__(64 * NW, OCC) attn_train_dkv_kernel(const TrainP p) {
-  constexpr int NT = 64 * NW;
-  __shared__ __attribute__((aligned(16))) float sQ[2][TT * LP];
-  __shared__ __attribute__((aligned(16))) float sO[2][TT * LPO];
+template <int D, bool SPILL>
+__global__ void __launch_bounds__(kNT, min_waves(D, DKV)) attn_train_dkv_kernel(const TrainP p) {
+  static_assert(!SPILL || D == 64, "the dS spill exists at 64 only");
+  constexpr int DB = D / 32, HD = D / 2, LD = D + 4, LDO = 2 * D + 4;
+  constexpr bool V2 = keep_v2(D);
+  __shared__ __attribute__((aligned(16))) float sQ[2][TT * LD];
+  __shared__ __attribute__((aligned(16))) float sO[2][TT * LDO];
   __shared__ float sL[2][TT], sD[2][TT];
-  const int t = xcd_remap(blockIdx.x, p.nblk);
-  const long long bh = t / p.nb;
+  const int t0 = xcd_remap(blockIdx.x, p.nblk);
+  const long long bh = t0 / p.nb;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5, r32 = lane & 31;
-  const int key = (t % p.nb) * 32 * NW + wave * 32 + r32;
+  const int key = (t0 % p.nb) * kRowsWG + wave * 32 + r32;
   const bool kv = key < p.Ns;
-  float kr[32], vr[32], vr2[32];
-  load_half_row(kr, p.k + bh * p.Ns * 64, key, kv, h, kLog2e);
-  load_half_row(vr, p.v + bh * p.Ns * 64, key, kv, h, 1.0f);
+  float kr[HD], vr[HD], vr2[V2 ? HD : 1];
+  load_half_row(kr, p.k + bh * p.Ns * D, key, kv, h, kLog2e);
+  load_half_row(vr, p.v + bh * p.Ns * D, key, kv, h, 1.0f);
+  if constexpr (V2) {
 #pragma unroll
-  for (int s = 0; s < 32; ++s) vr2[s] = vr[s] * vr[s];  // V'^2 once (the wave's keys are fixed)
-  const float* qb = p.q + bh * p.Nc * 64;
-  const float* ob = p.dmo + bh * p.Nc * 128;
+    for (int s = 0; s < HD; ++s) vr2[s] = vr[s] * vr[s];  // V'^2 once (the wave's keys are fixed)
+  }
+  auto v2 = [&](int s) {
+    if constexpr (V2) return vr2[s];
+    else return vr[s] * vr[s];
+  };
+  const float* qb = p.q + bh * p.Nc * D;
+  const float* ob = p.dmo + bh * p.Nc * 2 * D;
   const float* lb = p.lse + bh * p.Nc;
   const float* db = p.dd + bh * p.Nc;
-  f32x16 G1[2] = {f32x16{}, f32x16{}}, G2[2] = {f32x16{}, f32x16{}}, dK[2] = {f32x16{}, f32x16{}};
-  Stager<NT, 64, SPILL> gq;
-  Stager<NT, 128, SPILL> go;
+  f32x16 G1[DB], G2[DB], dK[DB];
+#pragma unroll
+  for (int i = 0; i < DB; ++i) G1[i] = G2[i] = dK[i] = f32x16{};
+  Stager<D, SPILL> gq;
+  Stager<2 * D, SPILL> go;
   float gl = INFINITY, gd = 0.f;
   // With SPILL the loop body is branch-free around global memory (clamped loads, the tile after
   // the last one loaded and discarded, range-checked buffer stores for dS): the wait before the
@@ -375,7 +437,7 @@ __global__ void __launch_bounds__(64 * NW, OCC) attn_train_dkv_kernel(const Trai
   auto load = [&](int q0) {
     gq.load(qb, q0, p.Nc, tid);
     go.load(ob, q0, p.Nc, tid);
-    const int qi = q0 + (tid & (TT - 1));
+    const int qi = q0 + (SPILL ? tid & (TT - 1) : tid);  // SPILL: every thread loads (no branch)
     if constexpr (SPILL) {
       const float l0 = lb[min(qi, p.Nc - 1)], d0 = db[min(qi, p.Nc - 1)];
       gl = qi < p.Nc ? l0 : INFINITY;  // padded query: P = 0
@@ -413,17 +475,17 @@ __global__ void __launch_bounds__(64 * NW, OCC) attn_train_dkv_kernel(const Trai
     if (SPILL || nxt) load((t + 1) * TT);
     // S (queries x keys) = Q . K^T, dA (queries x keys) = [dM' | dE2'] . [V' | V'^2]^T
     f32x16 S = {}, dA = {};
-    const float* qrow = sQ[cb] + r32 * LP + 32 * h;
-    const float* orow = sO[cb] + r32 * LPO + 32 * h;
+    const float* qrow = sQ[cb] + r32 * LD + HD * h;
+    const float* orow = sO[cb] + r32 * LDO + HD * h;
 #pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const f32x4 qq = ld4(qrow + 4 * i), o1 = ld4(orow + 4 * i), o2 = ld4(orow + 64 + 4 * i);
+    for (int i = 0; i < HD / 4; ++i) {
+      const f32x4 qq = ld4(qrow + 4 * i), o1 = ld4(orow + 4 * i), o2 = ld4(orow + D + 4 * i);
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const int s = 4 * i + e;
         S = mfma(qq[e], kr[s], S);
         dA = mfma(o1[e], vr[s], dA);
-        dA = mfma(o2[e], vr2[s], dA);
+        dA = mfma(o2[e], v2(s), dA);
       }
     }
     f32x16 P, dS;
@@ -443,14 +505,14 @@ __global__ void __launch_bounds__(64 * NW, OCC) attn_train_dkv_kernel(const Trai
     // G1^T, G2^T (c x keys) += [dM' | dE2']^T (c x queries) . P;  dK^T += Q^T . dS
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const float* o = sO[cb] + acc_row(r, h) * LPO + r32;
-      const float* qq = sQ[cb] + acc_row(r, h) * LP + r32;
-      G1[0] = mfma(o[0], P[r], G1[0]);
-      G1[1] = mfma(o[32], P[r], G1[1]);
-      G2[0] = mfma(o[64], P[r], G2[0]);
-      G2[1] = mfma(o[96], P[r], G2[1]);
-      dK[0] = mfma(qq[0], dS[r], dK[0]);
-      dK[1] = mfma(qq[32], dS[r], dK[1]);
+      const float* o = sO[cb] + acc_row(r, h) * LDO + r32;
+      const float* qq = sQ[cb] + acc_row(r, h) * LD + r32;
+#pragma unroll
+      for (int b = 0; b < DB; ++b) {
+        G1[b] = mfma(o[32 * b], P[r], G1[b]);
+        G2[b] = mfma(o[D + 32 * b], P[r], G2[b]);
+        dK[b] = mfma(qq[32 * b], dS[r], dK[b]);
+      }
     }
     if (nxt) store(cb ^ 1);
     lds_barrier();
@@ -458,24 +520,7 @@ __global__ void __launch_bounds__(64 * NW, OCC) attn_train_dkv_kernel(const Trai
   TRAIN_STAMP(1);
   if (!kv) return;
   const long long row = bh * p.Ns + key;
-  const float* vg = p.v + row * 64;
-  float* dvr = p.dv + row * 64;
-  float* dkr = p.dk + row * 64;
-#pragma unroll
-  for (int cb = 0; cb < 2; ++cb)
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const int c0 = 32 * cb + 8 * g + 4 * h;
-      const f32x4 vv = ld4(vg + c0);
-      f32x4 a, b;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        a[e] = G1[cb][4 * g + e] + 2.0f * vv[e] * G2[cb][4 * g + e];
-        b[e] = dK[cb][4 * g + e];
-      }
-      st4(dvr + c0, a);
-      st4(dkr + c0, b);
-    }
+  store_dkv(p.v + row * D, p.dv + row * D, p.dk + row * D, h, G1, G2, dK);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -688,36 +733,62 @@ __global__ void __launch_bounds__(256, 1) attn_train_dkv_dma_kernel(const TrainP
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the clamped DMA past the end has landed
   if (!kv) return;
   const long long row = bh * p.Ns + key;
-  const float* vg = p.v + row * 64;
-  float* dvr = p.dv + row * 64;
-  float* dkr = p.dk + row * 64;
-#pragma unroll
-  for (int cb = 0; cb < 2; ++cb)
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const int c0 = 32 * cb + 8 * g + 4 * h;
-      const f32x4 vv = ld4(vg + c0);
-      f32x4 a, b;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        a[e] = G1[cb][4 * g + e] + 2.0f * vv[e] * G2[cb][4 * g + e];
-        b[e] = dK[cb][4 * g + e];
-      }
-      st4(dvr + c0, a);
-      st4(dkr + c0, b);
-    }
+  store_dkv(p.v + row * 64, p.dv + row * 64, p.dk + row * 64, h, G1, G2, dK);
 }
 
-constexpr int kNW = 4;
 // per-(b, h) dS slice addressed by 32-bit buffer offsets, with 0x7ffffff0 free as the drop offset
 constexpr long long kMaxSpillRows = (0x7fff0000LL / 4);
+// rows and tiles are indexed in int (row offsets are 64-bit): n + kRowsWG must not wrap
+constexpr int kMaxRows = 1 << 30;
 
-bool set_grid(TrainP& p, long long BH, int n) {
-  p.nb = (n + 32 * kNW - 1) / (32 * kNW);
+typedef void (*TrainKernel)(TrainP);
+
+// One kernel over the n rows (queries or keys) of each of BH (batch, head) pairs.
+int launch(const char* fn, TrainKernel kern, TrainP& p, long long BH, int n, mhada_stream_t s) {
+  p.nb = (n + kRowsWG - 1) / kRowsWG;
   const long long nblk = BH * p.nb;
-  if (nblk > (1LL << 31) - 1) return false;
+  if (nblk > (1LL << 31) - 1) return fail(std::string(fn) + ": grid too large");
   p.nblk = (int)nblk;
-  return true;
+  hipLaunchKernelGGL(kern, dim3(p.nblk), dim3(kNT), 0, (hipStream_t)s, p);
+  return check_launch(fn);
+}
+
+// The launchers take what their entry points (fn) checked: D is 32, 64 or 128.
+int launch_fwd(const char* fn, const float* q, const float* k, const float* v, const float* x, float* out, float* mo,
+               float* lse, int BH, int D, int Nc, int Ns, mhada_stream_t s) {
+  TrainP p = {};
+  p.q = q; p.k = k; p.v = v; p.x = x; p.out = out; p.mo = mo; p.lse = lse; p.Nc = Nc; p.Ns = Ns;
+  return launch(fn, D == 32 ? attn_train_fwd_kernel<32> : D == 64 ? attn_train_fwd_kernel<64> : attn_train_fwd_kernel<128>,
+                p, BH, Nc, s);
+}
+
+int launch_dq(const char* fn, const float* q, const float* k, const float* v, const float* lse, const float* dmo,
+              const float* dd, float* dq, int BH, int D, int Nc, int Ns, mhada_stream_t s) {
+  TrainP p = {};
+  p.q = q; p.k = k; p.v = v; p.lse = const_cast<float*>(lse); p.dmo = dmo; p.dd = dd; p.dq = dq; p.Nc = Nc; p.Ns = Ns;
+  return launch(fn, D == 32 ? attn_train_dq_kernel<32> : D == 64 ? attn_train_dq_kernel<64> : attn_train_dq_kernel<128>,
+                p, BH, Nc, s);
+}
+
+// ds (D = 64 only): the dS spill, by the LDS-DMA kernel (tuning train_dkv_dma, the default) or the
+// register-staged one; null: no spill.  Nc == 0 is fine: no query tile, dK = dV' = 0.
+int launch_dkv(const char* fn, const float* q, const float* k, const float* v, const float* lse, const float* dmo,
+               const float* dd, float* dk, float* dv, float* ds, int BH, int D, int Nc, int Ns, mhada_stream_t s) {
+  TrainP p = {};
+  p.q = q; p.k = k; p.v = v; p.lse = const_cast<float*>(lse); p.dmo = dmo; p.dd = dd; p.dk = dk; p.dv = dv; p.ds = ds;
+  p.Nc = Nc; p.Ns = Ns;
+  const TrainKernel kern = ds ? (tuning().train_dkv_dma ? attn_train_dkv_dma_kernel : attn_train_dkv_kernel<64, true>)
+                           : D == 32 ? attn_train_dkv_kernel<32, false>
+                           : D == 64 ? attn_train_dkv_kernel<64, false>
+                                     : attn_train_dkv_kernel<128, false>;
+  return launch(fn, kern, p, BH, Ns, s);
+}
+
+// The width and row checks of the _hd entries (fn ends in "_hd").
+int check_hd(const std::string& fn, int D, int Nc, int Ns) {
+  if (D != 32 && D != 128) return fail(fn + ": D must be 32 or 128 (64: " + fn.substr(0, fn.size() - 3) + ")");
+  if (Nc > kMaxRows || Ns > kMaxRows) return fail(fn + ": Nc, Ns above 2^30");
+  return MHADA_OK;
 }
 
 }  // namespace
@@ -726,62 +797,66 @@ bool set_grid(TrainP& p, long long BH, int n) {
 using namespace mhada;
 
 extern "C" int mhada_attn_train_fwd(const float* q, const float* k, const float* v, const float* x, float* out,
-                                    float* mo, float* lse, int BH, int Nc, int Ns, mhada_stream_t s_) {
+                                    float* mo, float* lse, int BH, int Nc, int Ns, mhada_stream_t s) {
   if (!q || !k || !v || !x || !out || !mo || !lse || BH <= 0 || Nc <= 0 || Ns <= 0)
     return fail("mhada_attn_train_fwd: bad args");
-  TrainP p = {};
-  p.q = q; p.k = k; p.v = v; p.x = x; p.out = out; p.mo = mo; p.lse = lse; p.Nc = Nc; p.Ns = Ns;
-  if (!set_grid(p, BH, Nc)) return fail("mhada_attn_train_fwd: grid too large");
-  hipLaunchKernelGGL(attn_train_fwd_kernel<kNW>, dim3(p.nblk), dim3(64 * kNW), 0, (hipStream_t)s_, p);
-  return check_launch("mhada_attn_train_fwd");
+  return launch_fwd("mhada_attn_train_fwd", q, k, v, x, out, mo, lse, BH, 64, Nc, Ns, s);
 }
 
 extern "C" int mhada_attn_train_bwd(const float* q, const float* k, const float* v, const float* lse,
                                     const float* dmo, const float* dd, float* dq, float* dk, float* dv, int BH,
-                                    int Nc, int Ns, mhada_stream_t s_) {
+                                    int Nc, int Ns, mhada_stream_t s) {
   if (!q || !k || !v || !lse || !dmo || !dd || !dq || !dk || !dv || BH <= 0 || Nc <= 0 || Ns <= 0)
     return fail("mhada_attn_train_bwd: bad args");
-  const hipStream_t s = (hipStream_t)s_;
-  TrainP p = {};
-  p.q = q; p.k = k; p.v = v; p.lse = const_cast<float*>(lse); p.dmo = dmo; p.dd = dd; p.dq = dq; p.dk = dk; p.dv = dv;
-  p.Nc = Nc; p.Ns = Ns;
-  if (!set_grid(p, BH, Nc)) return fail("mhada_attn_train_bwd: grid too large");
-  hipLaunchKernelGGL(attn_train_dq_kernel<kNW>, dim3(p.nblk), dim3(64 * kNW), 0, s, p);
-  if (!set_grid(p, BH, Ns)) return fail("mhada_attn_train_bwd: grid too large");
-  // 288 registers, one wave per SIMD, no spills (two waves per SIMD at 256 registers spilled 18
-  // and measured the same, tools/train_attn_bench.py)
-  hipLaunchKernelGGL((attn_train_dkv_kernel<kNW, 1, false>), dim3(p.nblk), dim3(64 * kNW), 0, s, p);
-  return check_launch("mhada_attn_train_bwd");
+  if (int rc = launch_dq("mhada_attn_train_bwd", q, k, v, lse, dmo, dd, dq, BH, 64, Nc, Ns, s)) return rc;
+  return launch_dkv("mhada_attn_train_bwd", q, k, v, lse, dmo, dd, dk, dv, nullptr, BH, 64, Nc, Ns, s);
 }
 
 extern "C" int mhada_attn_train_dq(const float* q, const float* k, const float* v, const float* lse, const float* dmo,
-                                   const float* dd, float* dq, int BH, int Nc, int Ns, mhada_stream_t s_) {
+                                   const float* dd, float* dq, int BH, int Nc, int Ns, mhada_stream_t s) {
   if (!q || !k || !v || !lse || !dmo || !dd || !dq || BH <= 0 || Nc <= 0 || Ns <= 0)
     return fail("mhada_attn_train_dq: bad args");
-  TrainP p = {};
-  p.q = q; p.k = k; p.v = v; p.lse = const_cast<float*>(lse); p.dmo = dmo; p.dd = dd; p.dq = dq;
-  p.Nc = Nc; p.Ns = Ns;
-  if (!set_grid(p, BH, Nc)) return fail("mhada_attn_train_dq: grid too large");
-  hipLaunchKernelGGL(attn_train_dq_kernel<kNW>, dim3(p.nblk), dim3(64 * kNW), 0, (hipStream_t)s_, p);
-  return check_launch("mhada_attn_train_dq");
+  return launch_dq("mhada_attn_train_dq", q, k, v, lse, dmo, dd, dq, BH, 64, Nc, Ns, s);
 }
 
 extern "C" int mhada_attn_train_dkv(const float* q, const float* k, const float* v, const float* lse,
                                     const float* dmo, const float* dd, float* dk, float* dv, float* ds, int BH,
-                                    int Nc, int Ns, mhada_stream_t s_) {
+                                    int Nc, int Ns, mhada_stream_t s) {
   if (!q || !k || !v || !lse || !dmo || !dd || !dk || !dv || !ds || BH <= 0 || Nc <= 0 || Ns <= 0)
     return fail("mhada_attn_train_dkv: bad args");
   if ((long long)(Nc + TT) * Ns > kMaxSpillRows)
     return fail("mhada_attn_train_dkv: (Nc + 32) * Ns above 2^29 - 2^14 (32-bit dS offsets)");
-  TrainP p = {};
-  p.q = q; p.k = k; p.v = v; p.lse = const_cast<float*>(lse); p.dmo = dmo; p.dd = dd; p.dk = dk; p.dv = dv;
-  p.ds = ds; p.Nc = Nc; p.Ns = Ns;
-  if (!set_grid(p, BH, Ns)) return fail("mhada_attn_train_dkv: grid too large");
-  if (tuning().train_dkv_dma)  // LDS-DMA form, two workgroups per CU (round 4)
-    hipLaunchKernelGGL(attn_train_dkv_dma_kernel, dim3(p.nblk), dim3(64 * kNW), 0, (hipStream_t)s_, p);
-  else
-    hipLaunchKernelGGL((attn_train_dkv_kernel<kNW, 1, true>), dim3(p.nblk), dim3(64 * kNW), 0, (hipStream_t)s_, p);
-  return check_launch("mhada_attn_train_dkv");
+  return launch_dkv("mhada_attn_train_dkv", q, k, v, lse, dmo, dd, dk, dv, ds, BH, 64, Nc, Ns, s);
+}
+
+extern "C" int mhada_attn_train_fwd_hd(const float* q, const float* k, const float* v, const float* x, float* out,
+                                       float* mo, float* lse, int BH, int D, int Nc, int Ns, mhada_stream_t s) {
+  if (!q || !k || !v || !x || !out || !mo || !lse || BH <= 0 || Nc < 0 || Ns <= 0)
+    return fail("mhada_attn_train_fwd_hd: bad args");
+  if (int rc = check_hd("mhada_attn_train_fwd_hd", D, Nc, Ns)) return rc;
+  if (Nc == 0) return MHADA_OK;
+  return launch_fwd("mhada_attn_train_fwd_hd", q, k, v, x, out, mo, lse, BH, D, Nc, Ns, s);
+}
+
+extern "C" int mhada_attn_train_bwd_hd(const float* q, const float* k, const float* v, const float* lse,
+                                       const float* dmo, const float* dd, float* dq, float* dk, float* dv, int BH,
+                                       int D, int Nc, int Ns, mhada_stream_t s) {
+  if (!q || !k || !v || !lse || !dmo || !dd || !dq || !dk || !dv || BH <= 0 || Nc < 0 || Ns <= 0)
+    return fail("mhada_attn_train_bwd_hd: bad args");
+  if (int rc = check_hd("mhada_attn_train_bwd_hd", D, Nc, Ns)) return rc;
+  if (Nc > 0)
+    if (int rc = launch_dq("mhada_attn_train_bwd_hd", q, k, v, lse, dmo, dd, dq, BH, D, Nc, Ns, s)) return rc;
+  return launch_dkv("mhada_attn_train_bwd_hd", q, k, v, lse, dmo, dd, dk, dv, nullptr, BH, D, Nc, Ns, s);
+}
+
+extern "C" int mhada_attn_train_dq_hd(const float* q, const float* k, const float* v, const float* lse,
+                                      const float* dmo, const float* dd, float* dq, int BH, int D, int Nc, int Ns,
+                                      mhada_stream_t s) {
+  if (!q || !k || !v || !lse || !dmo || !dd || !dq || BH <= 0 || Nc < 0 || Ns <= 0)
+    return fail("mhada_attn_train_dq_hd: bad args");
+  if (int rc = check_hd("mhada_attn_train_dq_hd", D, Nc, Ns)) return rc;
+  if (Nc == 0) return MHADA_OK;
+  return launch_dq("mhada_attn_train_dq_hd", q, k, v, lse, dmo, dd, dq, BH, D, Nc, Ns, s);
 }
 
 #ifdef ATTN_CLOCK

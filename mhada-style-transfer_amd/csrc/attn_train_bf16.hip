@@ -4,12 +4,12 @@
 //
 // Reference: AdaAttnMultiHead.forward (MHAdaSTr/network/adaDecoder.py:186-198) under
 // train_image.py:93-144 autograd inside torch.autocast(bfloat16): bmm in bf16, softmax in fp32.
-// The maths is attn_train.hip:1-23 / attn_train_hd.hip:5-14: per (batch, head), Q, X [Nc][64],
+// The maths is attn_train.hip:1-21 at D = 64: per (batch, head), Q, X [Nc][64],
 // K, V' [Ns][64] (V' centred by the caller),
 //   A = softmax(Q K^T)   M' = A V'   E2' = A V'^2   out' = sqrt(max(E2' - M'^2, 1e-6)) X + M'
 //   dA = dM'.V'^T + dE2'.(V'^2)^T   dS = P (dA - D_row)   dQ = dS K   dK = dS^T Q
 //   dV' = P^T dM' + 2 V' (P^T dE2')
-// The structure is attn_train_hd.hip's: a forward that keeps lse2, a query-stationary dQ kernel and
+// The structure is that of attn_train.hip's plain kernels: a forward that keeps lse2, a query-stationary dQ kernel and
 // a key-stationary dK / dV' kernel, both deterministic (no atomics); the Nc x Ns matrices never
 // reach memory and nothing is spilled (the backward recomputes S and dA).
 //

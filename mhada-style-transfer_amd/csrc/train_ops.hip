@@ -716,8 +716,8 @@ __global__ void __launch_bounds__(256) inb_apply_kernel(const float* __restrict_
 }
 
 // ======================================================================================
-// MHAda attention backward head: per row (bh, query) of D channels (64, or 32 | 128 for the head
-// widths of attn_train_hd.hip), with m = M', e2 = E2':
+// MHAda attention backward head: per row (bh, query) of D channels (32 | 64 | 128, the head
+// widths of attn_train.hip), with m = M', e2 = E2':
 //   var = e2 - m^2, sd = sqrt(max(var, 1e-6)), dx = dout sd,
 //   dvar = dout x 0.5 / sd where var >= 1e-6 (0 where the clamp is active), dm = dout - 2 m dvar,
 //   dmo = [dm | dvar], dd = sum_c (dm m + dvar e2).   min(D, 64) lanes per row (D = 64: one wave
@@ -1350,30 +1350,31 @@ extern "C" int mhada_instnorm_bwd(const float* dy, const float* y, const float* 
   return check_launch("mhada_instnorm_bwd/apply");
 }
 
+// The launch behind both bwd_prep entries (fn: the entry's name; D is 32, 64 or 128): min(D, 64)
+// lanes per row, so 4 rows per block at 64 and 128, 8 at 32.
+static int launch_bwd_prep(const char* fn, const float* dout, const float* x, const float* mo, float* dx, float* dmo,
+                           float* dd, long long rows, int D, mhada_stream_t s) {
+  const int rpb = D == 32 ? 8 : 4;  // rows per block
+  const long long nblk = (rows + rpb - 1) / rpb;
+  if (nblk > (1LL << 31) - 1) return fail(std::string(fn) + ": grid too large");
+  hipLaunchKernelGGL(D == 32 ? attn_bwd_prep_kernel<32> : D == 64 ? attn_bwd_prep_kernel<64> : attn_bwd_prep_kernel<128>,
+                     dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)s, dout, x, mo, dx, dmo, dd, rows);
+  return check_launch(fn);
+}
+
 extern "C" int mhada_attn_train_bwd_prep(const float* dout, const float* x, const float* mo, float* dx, float* dmo,
-                                         float* dd, long long rows, mhada_stream_t s_) {
+                                         float* dd, long long rows, mhada_stream_t s) {
   if (!dout || !x || !mo || !dx || !dmo || !dd || rows <= 0) return fail("mhada_attn_train_bwd_prep: bad args");
-  hipLaunchKernelGGL(attn_bwd_prep_kernel<64>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)s_, dout,
-                     x, mo, dx, dmo, dd, rows);
-  return check_launch("mhada_attn_train_bwd_prep");
+  return launch_bwd_prep("mhada_attn_train_bwd_prep", dout, x, mo, dx, dmo, dd, rows, 64, s);
 }
 
 extern "C" int mhada_attn_train_bwd_prep_hd(const float* dout, const float* x, const float* mo, float* dx, float* dmo,
-                                            float* dd, long long rows, int D, mhada_stream_t s_) {
+                                            float* dd, long long rows, int D, mhada_stream_t s) {
   if (!dout || !x || !mo || !dx || !dmo || !dd || rows < 0) return fail("mhada_attn_train_bwd_prep_hd: bad args");
   if (D != 32 && D != 128)
     return fail("mhada_attn_train_bwd_prep_hd: D must be 32 or 128 (64: mhada_attn_train_bwd_prep)");
   if (rows == 0) return MHADA_OK;
-  const int rpb = D == 32 ? 8 : 4;  // rows per block
-  const long long nblk = (rows + rpb - 1) / rpb;
-  if (nblk > (1LL << 31) - 1) return fail("mhada_attn_train_bwd_prep_hd: grid too large");
-  if (D == 32)
-    hipLaunchKernelGGL(attn_bwd_prep_kernel<32>, dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)s_, dout, x, mo, dx,
-                       dmo, dd, rows);
-  else
-    hipLaunchKernelGGL(attn_bwd_prep_kernel<128>, dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)s_, dout, x, mo,
-                       dx, dmo, dd, rows);
-  return check_launch("mhada_attn_train_bwd_prep_hd");
+  return launch_bwd_prep("mhada_attn_train_bwd_prep_hd", dout, x, mo, dx, dmo, dd, rows, D, s);
 }
 
 extern "C" int mhada_pos_embed_bwd(const float* g, float* gpos, int C, int bh, int bw, int oh, int ow,

@@ -175,7 +175,7 @@ def _softmax_or_cosine(q, k, activation: str):
 
 class MHAdaAttnFn(torch.autograd.Function):
     """The attention core of adaDecoder.py:186-198 on the HIP training kernels
-    (csrc/attn_train.hip; head widths 32 and 128: csrc/attn_train_hd.hip):
+    (csrc/attn_train.hip, one kernel family for the head widths 32, 64 and 128):
     out' = sqrt(max(E2' - M'^2, 1e-6)) * x + M' with M' = A V', E2' = A V'^2, A = softmax(q k^T).
     q, x (BH, Nc, D); k, v (BH, Ns, D), v centred, D = 64 | 32 | 128.
     A is never stored: the backward recomputes it from the saved row normaliser.  When neither k nor

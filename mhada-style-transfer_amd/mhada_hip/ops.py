@@ -946,7 +946,7 @@ def _train_hd_width(what: str, t: torch.Tensor) -> int:
 
 
 def attn_train_fwd_hd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, x: torch.Tensor):
-    """``mhada_attn_train_fwd_hd``: ``attn_train_fwd`` at head width D = 32 | 128 (csrc/attn_train_hd.hip):
+    """``mhada_attn_train_fwd_hd``: ``attn_train_fwd`` at head width D = 32 | 128 (csrc/attn_train.hip):
     q, x (BH, Nc, D); k, v (BH, Ns, D) with v centred.  Returns out' (BH, Nc, D), [M' | E2'] (BH, Nc, 2D),
     lse2 (BH, Nc).  One fp32-MFMA kernel; the TRAIN_FWD_* knobs are 64-wide only."""
     _rows64(q, k, v, x)

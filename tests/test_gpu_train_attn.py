@@ -298,3 +298,92 @@ def test_transpose64_split3_is_split_of_transpose(BH, N):
     kt = ops.transpose64(x)
     ldt = kt.shape[-1]
     assert torch.equal(ops.transpose64_split3(x), ops.split3_rows(kt.view(BH * 64, ldt)))
+
+
+@pytest.mark.parametrize("BH,Nc,Ns,scale", [(3, 100, 70, 0.4), (2, 33, 4, 0.5), (2, 200, 160, 0.7)])
+def test_attn_train_plain64_chain_vs_fp64(monkeypatch, BH, Nc, Ns, scale):
+    """The plain 64-wide kernels, which MHAdaAttnFn's defaults (SPLIT3 forward, spill backward) do not
+    reach: mhada_attn_train_fwd (both TRAIN_FWD_* knobs off), mhada_attn_train_bwd_prep and the
+    recompute backward (spill=False) as one chain against fp64 autograd, to the file's bounds —
+    ragged query and key tiles, Ns below one 32-key tile with one query past a tile, two workgroups
+    per (b, h) on both grids.  attn_train_dq returns the bits of that backward's dq."""
+    monkeypatch.setattr(ops, "TRAIN_FWD_S3", False)
+    monkeypatch.setattr(ops, "TRAIN_FWD_VT", False)
+    g = torch.Generator().manual_seed(Nc * 7 + Ns + 64)
+    q = torch.randn(BH, Nc, 64, generator=g) * scale
+    k = torch.randn(BH, Ns, 64, generator=g) * scale
+    v = torch.randn(BH, Ns, 64, generator=g) * 3
+    v = v - v.mean(dim=1, keepdim=True)
+    x = torch.randn(BH, Nc, 64, generator=g)
+    dout = torch.randn(BH, Nc, 64, generator=g)
+    ts = [t.double().requires_grad_() for t in (q, k, v, x)]
+    ref = _ref(*ts)
+    ref.backward(dout.double())
+    qg, kg, vg, xg, dg = (t.cuda().contiguous() for t in (q, k, v, x, dout))
+    out, mo, lse = ops.attn_train_fwd(qg, kg, vg, xg)
+    dx, dmo, dd = ops.attn_train_bwd_prep(dg, xg, mo)
+    before = dict(ops.BWD_PATH_COUNTS)
+    dq, dk, dv = ops.attn_train_bwd(qg, kg, vg, lse, dmo, dd, spill=False)
+    assert ops.BWD_PATH_COUNTS["recompute"] == before["recompute"] + 1
+    assert torch.equal(ops.attn_train_dq(qg, kg, vg, lse, dmo, dd), dq)
+    # yardstick: the reference's own fp32 autograd (materialised A) on the same device
+    fs = [t.cuda().contiguous().requires_grad_() for t in (q, k, v, x)]
+    out32 = _ref(*fs)
+    out32.backward(dg)
+    torch.cuda.synchronize()
+    err, err32 = _rel(out.double().cpu(), ref.detach()), _rel(out32.double().cpu(), ref.detach())
+    print(f"out: err {err:.3e} err32 {err32:.3e}")
+    assert err < max(2e-4, 2 * err32)
+    for name, a, b, c in zip("qkvx", (dq, dk, dv, dx), ts, fs):
+        err = _rel(a.double().cpu(), b.grad)
+        err32 = _rel(c.grad.double().cpu(), b.grad)
+        print(f"d{name}: err {err:.3e} err32 {err32:.3e}")
+        assert err < max(2e-4, 4 * err32), (name, err, err32)
+
+
+def test_attn_train_plain64_leaves_guard_rows_intact(monkeypatch):
+    """test_attn_train_hd_leaves_guard_rows_intact for the plain 64-wide entries mhada_attn_train_fwd,
+    _bwd_prep, _bwd and _dq: Nc = 37 (a ragged 32-query tile), Ns = 5 (below one key tile), every
+    output between NaN-pattern guard rows at each (b, h) boundary (the entries are called per slice
+    on pointers into the guarded buffers): the guards keep their pattern, every payload element is
+    written, and the per-slice results are the batched ops' bits."""
+    from mhada_hip import _lib
+    from test_gpu_train_heads import Guarded
+    BH, Nc, Ns = 3, 37, 5
+    g = torch.Generator().manual_seed(37 + 64)
+    q, k, v, x, dout = (torch.randn(BH, n, 64, generator=g).cuda() * s
+                        for n, s in ((Nc, 0.5), (Ns, 0.5), (Ns, 3.0), (Nc, 1.0), (Nc, 1.0)))
+    v = (v - v.mean(dim=1, keepdim=True)).contiguous()
+    out, mo, lse = Guarded(BH, Nc, 64), Guarded(BH, Nc, 128), Guarded(BH, Nc, 1)
+    dx, dmo, dd = Guarded(BH, Nc, 64), Guarded(BH, Nc, 128), Guarded(BH, Nc, 1)
+    dq, dq1, dk, dv = Guarded(BH, Nc, 64), Guarded(BH, Nc, 64), Guarded(BH, Ns, 64), Guarded(BH, Ns, 64)
+    lib = _lib.load()
+    st = torch.cuda.current_stream().cuda_stream
+    for i in range(BH):
+        p = lambda t: t.data_ptr()  # noqa: E731
+        rc = lib.mhada_attn_train_fwd(p(q[i]), p(k[i]), p(v[i]), p(x[i]), p(out.slice(i)), p(mo.slice(i)),
+                                      p(lse.slice(i)), 1, Nc, Ns, st)
+        assert rc == 0, lib.mhada_last_error()
+        rc = lib.mhada_attn_train_bwd_prep(p(dout[i]), p(x[i]), p(mo.slice(i)), p(dx.slice(i)), p(dmo.slice(i)),
+                                           p(dd.slice(i)), Nc, st)
+        assert rc == 0, lib.mhada_last_error()
+        rc = lib.mhada_attn_train_bwd(p(q[i]), p(k[i]), p(v[i]), p(lse.slice(i)), p(dmo.slice(i)), p(dd.slice(i)),
+                                      p(dq.slice(i)), p(dk.slice(i)), p(dv.slice(i)), 1, Nc, Ns, st)
+        assert rc == 0, lib.mhada_last_error()
+        rc = lib.mhada_attn_train_dq(p(q[i]), p(k[i]), p(v[i]), p(lse.slice(i)), p(dmo.slice(i)), p(dd.slice(i)),
+                                     p(dq1.slice(i)), 1, Nc, Ns, st)
+        assert rc == 0, lib.mhada_last_error()
+    torch.cuda.synchronize()
+    for t in (out, mo, lse, dx, dmo, dd, dq, dq1, dk, dv):
+        t.check()
+    # the per-slice calls return what the batched ops return
+    monkeypatch.setattr(ops, "TRAIN_FWD_S3", False)
+    monkeypatch.setattr(ops, "TRAIN_FWD_VT", False)
+    o2, mo2, lse2 = ops.attn_train_fwd(q, k, v, x)
+    dx2, dmo2, dd2 = ops.attn_train_bwd_prep(dout, x, mo2)
+    dq2, dk2, dv2 = ops.attn_train_bwd(q, k, v, lse2, dmo2, dd2, spill=False)
+    dq3 = ops.attn_train_dq(q, k, v, lse2, dmo2, dd2)
+    for i in range(BH):
+        for a, b in ((out, o2), (mo, mo2), (dx, dx2), (dmo, dmo2), (dq, dq2), (dq1, dq3), (dk, dk2), (dv, dv2)):
+            assert torch.equal(a.slice(i), b[i])
+        assert torch.equal(lse.slice(i).view(-1), lse2[i]) and torch.equal(dd.slice(i).view(-1), dd2[i])

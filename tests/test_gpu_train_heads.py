@@ -1,5 +1,5 @@
-"""Training at head widths 32 and 128 (16- and 4-head models): the kernels of csrc/attn_train_hd.hip
-through MHAdaAttnFn, the grouped head projection at d = 32 | 128, the fused block and one Trainer step.
+"""Training at head widths 32 and 128 (16- and 4-head models): the D = 32 | 128 kernels of
+csrc/attn_train.hip through MHAdaAttnFn, the grouped head projection at d = 32 | 128, the fused block and one Trainer step.
 
 Bounds are those of test_gpu_train_attn.py (its docstring): fp32 MFMA against fp64, outputs
 < max(2e-4, 2 err32) and gradients < max(2e-4, 4 err32) of the tensor's max magnitude, err32 the

@@ -1,5 +1,5 @@
 """A/B of training a 4- / 16-head MHAda block (head_dim 128 / 32) on the HIP attention kernels
-(autograd_path.TRAIN_ATTN = "hip": csrc/attn_train_hd.hip, the grouped head projection) against the
+(autograd_path.TRAIN_ATTN = "hip": csrc/attn_train.hip at D = 32 | 128, the grouped head projection) against the
 per-head aten loop ("torch": what these widths ran before the kernels existed — the baseline).
 
 One process, interleaved rounds: every configuration runs once per round, block forward + backward,
