@@ -320,6 +320,13 @@ def test_conv3x3_wino(pad_mode, pad, B, H, W, Ci, Co, ldc):
         ref = torch.relu(ref) if relu else ref
         assert rel(y[..., :Co].permute(0, 3, 1, 2), ref) < 2e-6
         assert bool((y[..., Co:] == 7.0).all())
+        # the same U without the plane image: wino4_kernel at every Cin (with Cin % 16 == 0 the call above
+        # takes wino_s3_kernel)
+        u4 = ops.wino_weights(wp).clone()
+        assert getattr(u4, "split3", None) is None
+        y4 = ops.conv3x3_wino(x, u4, bias, relu, pad_mode, pad, out=torch.full((B, Ho, Wo, ldc), 7.0, device=DEV))
+        assert rel(y4[..., :Co].permute(0, 3, 1, 2), ref) < 2e-6
+        assert bool((y4[..., Co:] == 7.0).all())
         # the folded ReLU adjoint (relu_mask): zero exactly where mask <= 0, the same values elsewhere
         outm = torch.full((B, Ho, Wo, ldc), 7.0, device=DEV)
         ym = ops.conv3x3_wino(x, ops.wino_weights(wp), bias, relu, pad_mode, pad, out=outm, relu_mask=mask)

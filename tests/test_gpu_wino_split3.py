@@ -62,8 +62,8 @@ def check(x, w, b, pad_mode, pad, ldc, tag):
         print(f"{tag} {pad_mode}{pad} B{B} {H}x{W} {Ci}->{Co} relu={int(relu)}: split3 {e:.3e} wino4 {e4:.3e} "
               f"ratio {e / max(e4, 1e-30):.2f}")
         worst = max(worst, e / max(e4, 1e-30))
-        assert e < BOUND
-        assert bool((y[..., Co:] == 7.0).all())
+        assert e < BOUND and e4 < BOUND
+        assert bool((y[..., Co:] == 7.0).all()) and bool((y4[..., Co:] == 7.0).all())
         # knob off: the parent's kernel and bits
         assert torch.equal(y0, y4)
         # two runs of the new kernel agree bit for bit
