@@ -145,6 +145,12 @@ int mhada_layernorm(const float* x, void* y, int y_dtype, const float* gamma, co
  * width returns MHADA_ERR_ARG. */
 int mhada_vit_batch_attn(const void* qkv, void* out, int dtype, int L, int ntok, int heads,
                          int head_dim, mhada_stream_t stream);
+/* The fp32 form with the result written as its three bf16 planes instead of fp32 rows (the out-projection's
+ * SPLIT3 GEMM operand; bit-identical to mhada_split3_rows of mhada_vit_batch_attn's fp32 out): plane p of
+ * element e of out at planes[p * pstride + e], pstride >= L * ntok * C.  head_dim 64 and L <= 8 only (any
+ * other shape returns MHADA_ERR_ARG; the caller then keeps the fp32 entry). */
+int mhada_vit_batch_attn_split3(const float* qkv, void* planes, long long pstride, int L, int ntok, int heads,
+                                int head_dim, mhada_stream_t stream);
 
 /* PosEmbedding (vit.py:81-102): bilinear (align_corners=False) resize of pos (C, bh, bw)
  * fp32 to (oh, ow), written token-major out[oh*ow][C] fp32 (copy when sizes match). */
@@ -262,6 +268,12 @@ int mhada_kv_proj_split3(const float* fs, const float* mu_s, const float* wkv, c
 int mhada_attn_split3(const float* q, const void* img, const float* fcs, const float* fcs_mu,
                       const float* fcs_rstd, const float* v_mu, float* out, int B, int H, int Nc, int Ns,
                       mhada_stream_t stream);
+/* mhada_attn_split3 with out written as its three bf16 planes [3][B Nc][64H] (p0 = bf16(out),
+ * p1 = bf16(out - p0), p2 = bf16(out - p0 - p1); bit-identical to mhada_split3_rows of mhada_attn_split3's
+ * out) and no fp32 rows: the A operand of the out_conv SPLIT3 GEMM. */
+int mhada_attn_split3_planes(const float* q, const void* img, const float* fcs, const float* fcs_mu,
+                             const float* fcs_rstd, const float* v_mu, void* planes, int B, int H, int Nc, int Ns,
+                             mhada_stream_t stream);
 
 /* The cosine activation (CosineSimilarity, adaDecoder.py:20-34) in its linear form (ABI 14):
  * A[i][j] = (q^_i.k^_j + 1) / l_i with l_i = q^_i.sum_j k^_j + Ns, so A V' and A V'^2 need only the

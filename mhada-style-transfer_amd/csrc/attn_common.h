@@ -145,7 +145,9 @@ MHADA_DEV int fsq_key(int r, int t) { return 16 * (r >> 3) + 4 * ((r >> 2) & 1) 
 
 // Epilogue of the 16x16x32 layout: O[qg][dvb] holds O^T[dv][q] for q = q0 + 16 qg + r16,
 // dv = 16 dvb + 4g + e (dvb 0-3: sum p v', 4-7: sum p v'^2); lt = the full row sums.
-template <typename T>
+// PLANES (T = float): p.out is bf16 [3][B Nc][C], the fp32 result as its three round-to-nearest planes
+// (r0 = bf16(res), r1 = bf16(res - r0), r2 = bf16(res - r0 - r1): the SPLIT3 GEMM's A operand), no fp32 row.
+template <typename T, bool PLANES = false>
 MHADA_DEV void attn_epilogue_q(const AttnP& p, const f32x4 (&O)[2][8], const float (&lt)[2], int b, int hh, int q0,
                                int g, int r16) {
   const int C = p.H * 64;
@@ -174,7 +176,22 @@ MHADA_DEV void attn_epilogue_q(const AttnP& p, const f32x4 (&O)[2][8], const flo
         const float sd = sqrtf(fmaxf(e2 - m1 * m1, 1e-6f));
         res[e] = sd * ((f[e] - m4[e]) * r4[e]) + (m1 + v4[e]);
       }
-      if constexpr (sizeof(T) == 4) {
+      if constexpr (PLANES) {
+        static_assert(sizeof(T) == 4, "planes split an fp32 result");
+        const long long ps = (long long)p.B * p.Nc * C;
+        bf16* pl = reinterpret_cast<bf16*>(p.out) + ((long long)b * p.Nc + q) * C + hh * 64 + dv0;
+        bf16x4 r0, r1, r2;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          r0[e] = (bf16)res[e];
+          const float d = res[e] - (float)r0[e];
+          r1[e] = (bf16)d;
+          r2[e] = (bf16)(d - (float)r1[e]);
+        }
+        *reinterpret_cast<bf16x4*>(pl) = r0;
+        *reinterpret_cast<bf16x4*>(pl + ps) = r1;
+        *reinterpret_cast<bf16x4*>(pl + 2 * ps) = r2;
+      } else if constexpr (sizeof(T) == 4) {
         *reinterpret_cast<f32x4*>(orow + dv0) = f32x4{res[0], res[1], res[2], res[3]};
       } else {
         *reinterpret_cast<bf16x4*>(orow + dv0) = bf16x4{(bf16)res[0], (bf16)res[1], (bf16)res[2], (bf16)res[3]};

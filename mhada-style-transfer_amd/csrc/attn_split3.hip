@@ -410,7 +410,9 @@ MHADA_DEV void attn_train_epilogue_q(const AttnP& p, const f32x4 (&O)[2][8], con
 // MFMAs — bit-identical, 1.6-3.4 % faster at the bench shapes than the two groups in sequence
 // (tools/attn_s3_variants_interleaved.py, profiles/r06_attn_s3_interleave_ab.log; a full-tile
 // interleave with the Q K^T of group 1 beside the split of group 0 measured no better).
-template <int NW, bool TRAIN = false, bool QK32 = false, int ACC = 0, int IL = 0>
+// PLANES (inference): the output as its three bf16 planes [3][B Nc][64 H] (attn_epilogue_q PLANES), the A
+// operand of the out_conv SPLIT3 GEMM, instead of fp32 rows.
+template <int NW, bool TRAIN = false, bool QK32 = false, int ACC = 0, int IL = 0, bool PLANES = false>
 __global__ void __launch_bounds__(64 * NW, 1) attn_s3_kernel(const AttnP p) {
   constexpr int TK = kS3Tk;
   constexpr int KPL = TK * 64, VPL = 128 * TK;                // bf16 elements per plane
@@ -684,7 +686,7 @@ __global__ void __launch_bounds__(64 * NW, 1) attn_s3_kernel(const AttnP p) {
   }
   if (__any(!(lt[0] <= kShiftSumThr) || !(lt[1] <= kShiftSumThr))) attn_exact_q3<QK32>(p, kp, vp, qf, qreg, O, lt, mx, g, r16);
   if constexpr (TRAIN) attn_train_epilogue_q(p, O, lt, mx, bh, q0, g, r16);
-  else attn_epilogue_q<float>(p, O, lt, b, hh, q0, g, r16);
+  else attn_epilogue_q<float, PLANES>(p, O, lt, b, hh, q0, g, r16);
 }
 
 static int s3_num_cus() {
@@ -722,28 +724,46 @@ extern "C" int mhada_kv_proj_split3(const float* fs, const float* mu_s, const fl
   return check_launch("mhada_kv_proj_split3");
 }
 
-extern "C" int mhada_attn_split3(const float* q, const void* img, const float* fcs, const float* fcs_mu,
-                                 const float* fcs_rstd, const float* v_mu, float* out, int B, int H, int Nc, int Ns,
-                                 mhada_stream_t s_) {
+static int attn_split3_launch(const char* name, const float* q, const void* img, const float* fcs, const float* fcs_mu,
+                              const float* fcs_rstd, const float* v_mu, void* out, bool planes, int B, int H, int Nc,
+                              int Ns, mhada_stream_t s_) {
   if (!q || !img || !fcs || !fcs_mu || !fcs_rstd || !v_mu || !out || B <= 0 || H <= 0 || Nc <= 0 || Ns <= 0)
-    return fail("mhada_attn_split3: bad args");
+    return fail(std::string(name) + ": bad args");
   AttnP p = {};
   p.q = q; p.kv = img; p.vt = img; p.fcs = fcs; p.fcs_mu = fcs_mu; p.fcs_rstd = fcs_rstd; p.v_mu = v_mu;
   p.out = out; p.B = B; p.H = H; p.Nc = Nc; p.Ns = Ns;
   p.ldt = (Ns + 63) / 64 * 64;
-  if (384LL * p.ldt >= (1LL << 31)) return fail("mhada_attn_split3: Ns too large for 32-bit plane offsets");
+  if (384LL * p.ldt >= (1LL << 31)) return fail(std::string(name) + ": Ns too large for 32-bit plane offsets");
   // waves per block as mhada_attn: tuning attn_waves, 0 = 8, or 4 when the 8-wave grid has fewer
   // blocks than CUs
   int nw = tuning().attn_waves;
   if (nw == 0) nw = (long long)B * H * ((Nc + 255) / 256) < s3_num_cus() ? 4 : 8;
   p.nqb = (Nc + 32 * nw - 1) / (32 * nw);
   const long long nblk = (long long)B * H * p.nqb;
-  if (nblk > (1LL << 31) - 1) return fail("mhada_attn_split3: grid too large");
+  if (nblk > (1LL << 31) - 1) return fail(std::string(name) + ": grid too large");
   p.nblk = (int)nblk;
   const hipStream_t s = (hipStream_t)s_;
-  if (nw == 8) hipLaunchKernelGGL((attn_s3_kernel<8, false, false, 0, 1>), dim3(p.nblk), dim3(512), 0, s, p);
-  else hipLaunchKernelGGL((attn_s3_kernel<4, false, false, 0, 1>), dim3(p.nblk), dim3(256), 0, s, p);
-  return check_launch("mhada_attn_split3");
+  if (planes) {
+    if (nw == 8) hipLaunchKernelGGL((attn_s3_kernel<8, false, false, 0, 1, true>), dim3(p.nblk), dim3(512), 0, s, p);
+    else hipLaunchKernelGGL((attn_s3_kernel<4, false, false, 0, 1, true>), dim3(p.nblk), dim3(256), 0, s, p);
+  } else {
+    if (nw == 8) hipLaunchKernelGGL((attn_s3_kernel<8, false, false, 0, 1>), dim3(p.nblk), dim3(512), 0, s, p);
+    else hipLaunchKernelGGL((attn_s3_kernel<4, false, false, 0, 1>), dim3(p.nblk), dim3(256), 0, s, p);
+  }
+  return check_launch(name);
+}
+
+extern "C" int mhada_attn_split3(const float* q, const void* img, const float* fcs, const float* fcs_mu,
+                                 const float* fcs_rstd, const float* v_mu, float* out, int B, int H, int Nc, int Ns,
+                                 mhada_stream_t s_) {
+  return attn_split3_launch("mhada_attn_split3", q, img, fcs, fcs_mu, fcs_rstd, v_mu, out, false, B, H, Nc, Ns, s_);
+}
+
+extern "C" int mhada_attn_split3_planes(const float* q, const void* img, const float* fcs, const float* fcs_mu,
+                                        const float* fcs_rstd, const float* v_mu, void* planes, int B, int H, int Nc,
+                                        int Ns, mhada_stream_t s_) {
+  return attn_split3_launch("mhada_attn_split3_planes", q, img, fcs, fcs_mu, fcs_rstd, v_mu, planes, true, B, H, Nc, Ns,
+                            s_);
 }
 
 // Training forward as SPLIT3 products (the contract of mhada_attn_train_fwd_vt, attn.hip): q, x

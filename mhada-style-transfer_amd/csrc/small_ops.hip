@@ -191,9 +191,11 @@ __global__ void __launch_bounds__(256) vit_batch_copy_v_kernel(const uint4* __re
 // Small-batch form (L <= 8, every bench/training config): each (token, head) reads q, k, v
 // once — q/k staged in LDS, v in registers — and the L x L scores are computed in parallel with
 // lane = (i, j); the softmax over j is an 8-lane group reduction.
-template <typename T>
-__global__ void __launch_bounds__(256) vit_batch_attn_small_kernel(const T* __restrict__ qkv, T* __restrict__ out,
-                                                                   int L, int ntok, int heads) {
+// PLANES: the fp32 result as its three bf16 planes (the split of split3_rows_kernel) at out_ (bf16),
+// plane stride pstride elements, instead of a T row.
+template <typename T, bool PLANES>
+MHADA_DEV void vit_batch_attn_small_body(const T* __restrict__ qkv, void* __restrict__ out_, long long pstride,
+                                         int L, int ntok, int heads) {
   constexpr int D = 64;
   __shared__ float sq[4][8][D + 1];
   __shared__ float sk[4][8][D + 1];
@@ -239,8 +241,56 @@ __global__ void __launch_bounds__(256) vit_batch_attn_small_kernel(const T* __re
     float o = 0.f;
 #pragma unroll
     for (int c = 0; c < 8; ++c) o = fmaf(sp[wv][r][c], vr[c], o);
-    out[((long long)r * ntok + n) * C + hh * D + lane] = from_f32<T>(o);
+    const long long at = ((long long)r * ntok + n) * C + hh * D + lane;
+    if constexpr (PLANES) {
+      bf16* pl = reinterpret_cast<bf16*>(out_) + at;
+      const bf16 a = (bf16)o;
+      const float r1 = o - (float)a;
+      const bf16 b = (bf16)r1;
+      pl[0] = a;
+      pl[pstride] = b;
+      pl[2 * pstride] = (bf16)(r1 - (float)b);
+    } else {
+      reinterpret_cast<T*>(out_)[at] = from_f32<T>(o);
+    }
   }
+}
+
+template <typename T>
+__global__ void __launch_bounds__(256) vit_batch_attn_small_kernel(const T* __restrict__ qkv, T* __restrict__ out,
+                                                                   int L, int ntok, int heads) {
+  vit_batch_attn_small_body<T, false>(qkv, out, 0, L, ntok, heads);
+}
+
+// The fp32 small-batch form with plane output (mhada_vit_batch_attn_split3).
+__global__ void __launch_bounds__(256) vit_batch_attn_small_s3_kernel(const float* __restrict__ qkv,
+                                                                      bf16* __restrict__ planes, long long pstride,
+                                                                      int L, int ntok, int heads) {
+  vit_batch_attn_small_body<float, true>(qkv, planes, pstride, L, ntok, heads);
+}
+
+// L = 1 with plane output: the V slice (the attention output bit for bit) split into its three planes,
+// four elements per thread (row4 = C / 4; 16-byte aligned qkv, 8-byte aligned plane rows).
+__global__ void __launch_bounds__(256) vit_batch_copy_v_s3_kernel(const float* __restrict__ qkv,
+                                                                  bf16* __restrict__ planes, long long pstride,
+                                                                  int ntok, int row4) {
+  const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= (long long)ntok * row4) return;
+  const long long n = idx / row4;
+  const int c = (int)(idx - n * row4);
+  const f32x4 v = *reinterpret_cast<const f32x4*>(qkv + 4 * (n * 3 * row4 + 2 * row4 + c));
+  bf16x4 a, b, d;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    a[e] = (bf16)v[e];
+    const float r = v[e] - (float)a[e];
+    b[e] = (bf16)r;
+    d[e] = (bf16)(r - (float)b[e]);
+  }
+  bf16* pl = planes + 4 * idx;
+  *reinterpret_cast<bf16x4*>(pl) = a;
+  *reinterpret_cast<bf16x4*>(pl + pstride) = b;
+  *reinterpret_cast<bf16x4*>(pl + 2 * pstride) = d;
 }
 
 // ---------------------------------------------------------------------------------------
@@ -915,6 +965,29 @@ extern "C" int mhada_vit_batch_attn(const void* qkv, void* out, int dtype, int L
                        ntok, heads);
   }
   return check_launch("mhada_vit_batch_attn");
+}
+
+extern "C" int mhada_vit_batch_attn_split3(const float* qkv, void* planes, long long pstride, int L, int ntok,
+                                           int heads, int head_dim, mhada_stream_t s_) {
+  hipStream_t s = (hipStream_t)s_;
+  if (!qkv || !planes || L <= 0 || ntok < 0 || heads <= 0) return fail("mhada_vit_batch_attn_split3: bad args");
+  if (head_dim != 64) return fail("mhada_vit_batch_attn_split3: head_dim must be 64");
+  if (L > 8) return fail("mhada_vit_batch_attn_split3: L must be <= 8");
+  if (pstride < (long long)L * ntok * heads * 64)
+    return fail("mhada_vit_batch_attn_split3: plane stride smaller than this call's output");
+  if (ntok == 0) return MHADA_OK;
+  bf16* pl = reinterpret_cast<bf16*>(planes);
+  if (L == 1 && aligned16(qkv) && aligned16(planes) && pstride % 4 == 0) {
+    const int row4 = heads * 16;
+    const long long n4 = (long long)ntok * row4;
+    hipLaunchKernelGGL(vit_batch_copy_v_s3_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, qkv, pl, pstride,
+                       ntok, row4);
+  } else {
+    const long long pairs = (long long)ntok * heads;
+    hipLaunchKernelGGL(vit_batch_attn_small_s3_kernel, dim3((unsigned)((pairs + 3) / 4)), dim3(256), 0, s, qkv, pl,
+                       pstride, L, ntok, heads);
+  }
+  return check_launch("mhada_vit_batch_attn_split3");
 }
 
 extern "C" int mhada_pos_embed(const float* pos, float* out, int C, int bh, int bw, int oh, int ow,

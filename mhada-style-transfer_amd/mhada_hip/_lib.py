@@ -64,6 +64,7 @@ SIGNATURES = {
     "mhada_gemm": (_I, [ctypes.POINTER(GemmArgs), _vp]),
     "mhada_layernorm": (_I, [_vp, _vp, _I, _vp, _vp, _I, _I, _F, _vp]),
     "mhada_vit_batch_attn": (_I, [_vp, _vp, _I, _I, _I, _I, _I, _vp]),
+    "mhada_vit_batch_attn_split3": (_I, [_vp, _vp, _c_ll, _I, _I, _I, _I, _vp]),
     "mhada_pos_embed": (_I, [_vp, _vp, _I, _I, _I, _I, _I, _vp]),
     "mhada_instnorm_stats": (_I, [_vp, _vp, _vp, _vp, _I, _I, _I, _I, _F, _vp]),
     "mhada_fold_block": (_I, [_vp] * 12 + [_F, _I, _I, _I, _vp]),
@@ -80,6 +81,7 @@ SIGNATURES = {
     "mhada_split3_rows": (_I, [_vp, _vp, _c_ll, _vp]),
     "mhada_split3_weight": (_I, [_vp, _vp, _I, _I, _I, _vp]),
     "mhada_attn_split3": (_I, [_vp] * 7 + [_I, _I, _I, _I, _vp]),
+    "mhada_attn_split3_planes": (_I, [_vp] * 7 + [_I, _I, _I, _I, _vp]),
     "mhada_attn_train_fwd": (_I, [_vp] * 7 + [_I, _I, _I, _vp]),
     "mhada_attn_train_fwd_vt": (_I, [_vp] * 8 + [_I, _I, _I, _vp]),
     "mhada_attn_train_fwd_split3": (_I, [_vp] * 8 + [_I, _I, _I, _vp]),

@@ -208,8 +208,13 @@ def vit_forward(vit, x: torch.Tensor) -> List[torch.Tensor]:
         else:
             hb = ops.layernorm(xs, L["ln1_g"], L["ln1_b"], dt, L["eps"])
             qkv = ops.linear(hb, L["w_qkv"], L["b_qkv"], dt)
-        att = ops.vit_batch_attn(qkv.view(B, N, 3 * C), B, N, L["heads"])
-        xs = ops.linear(att.view(B * N, C), L["w_o"], L["b_o"], torch.float32, residual=xs)
+        # the out-projection as a SPLIT3 GEMM too: the batch-axis attention writes the planes (no fp32 att)
+        if split_mlp and ops.F32_SPLIT_OUTPROJ and C == L["heads"] * HEAD_DIM and B <= ops.VIT_ATTN_SPLIT3_MAX_L:
+            att3 = ops.vit_batch_attn_split3(qkv.view(B, N, 3 * C), B, N, L["heads"])
+            xs = ops.linear_split3(att3, _w6(L, "w_o"), L["b_o"], torch.float32, residual=xs)
+        else:
+            att = ops.vit_batch_attn(qkv.view(B, N, 3 * C), B, N, L["heads"])
+            xs = ops.linear(att.view(B * N, C), L["w_o"], L["b_o"], torch.float32, residual=xs)
         if split_mlp:  # MLP1 writes its ReLU output as planes, MLP2 consumes them (SPLIT3 both)
             m1 = ops.linear_split3(ops.layernorm_split3(xs, L["ln2_g"], L["ln2_b"], L["eps"]), _w6(L, "w1"),
                                    L["b1"], dt, relu=True, out_planes=True)
@@ -334,6 +339,15 @@ def block_forward(blk, fc: _Feat, fs: Optional[_Feat], fcs: _Feat, dt: torch.dty
         ops.cosine_prep(q, None)
         with _timed("mhada_attn"):
             att = ops.cosine_attn(q, mom, fcs.t, mu_o, rstd_o, v_mu)  # [B][Nc][C] dt
+    elif split_attn and ops.F32_SPLIT_OUTPROJ and _split3_fills(B * Nc, C, dev):
+        # the attention writes its output as bf16 planes and out_conv runs as a SPLIT3 GEMM (no fp32 att)
+        with _timed("mhada_attn"):
+            att3 = ops.attn_split3_planes(q, img, Ns, fcs.t, mu_o, rstd_o, v_mu)  # [3][B Nc][C] bf16
+        if "w_out_split3" not in prep:
+            with torch.no_grad():
+                prep["w_out_split3"] = ops.split3_weight(prep["w_out"])
+        out = ops.linear_split3(att3, prep["w_out_split3"], prep["b_out"], torch.float32)
+        return _Feat(out.view(B, Nc, C), fc.h, fc.w)
     elif split_attn:
         with _timed("mhada_attn"):
             att = ops.attn_split3(q, img, Ns, fcs.t, mu_o, rstd_o, v_mu)  # [B][Nc][C] fp32

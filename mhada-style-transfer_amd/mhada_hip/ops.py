@@ -354,6 +354,13 @@ def layernorm(x: torch.Tensor, g: torch.Tensor, b: torch.Tensor, out_dtype: torc
 F32_SPLIT = True
 
 
+# The fp32 forward's two 512 x 512 out-projections (the ViT's attention out_proj and the MHAda block's
+# out_conv) as SPLIT3 GEMMs where their tiles fill the chip: the producing attention kernels write the
+# bf16 planes themselves (vit_batch_attn_split3, attn_split3_planes) and no fp32 copy.  False: both stay
+# on the fp32 MFMA GEMM, fed by fp32 attention outputs.
+F32_SPLIT_OUTPROJ = True
+
+
 def layernorm_split3(x: torch.Tensor, g: torch.Tensor, b: torch.Tensor, eps: float) -> torch.Tensor:
     """``mhada_layernorm`` with y_dtype MHADA_BF16X3: the fp32 LayerNorm of x as three bf16 planes
     [3][rows][cols] (y = p0 + p1 + p2 to 2^-25 relative), the A operand of ``linear_split3``."""
@@ -461,6 +468,23 @@ def vit_batch_attn(qkv: torch.Tensor, L: int, ntok: int, heads: int, groups: int
         _call("mhada_vit_batch_attn", qkv, qkv.data_ptr() + g * Lg * ntok * 3 * C * es,
               out.data_ptr() + g * Lg * ntok * C * es, dt_code(qkv.dtype), Lg, ntok, heads, C // heads)
     return out
+
+
+VIT_ATTN_SPLIT3_MAX_L = 8  # mhada_vit_batch_attn_split3 refuses longer batch axes (and head widths != 64)
+
+
+def vit_batch_attn_split3(qkv: torch.Tensor, L: int, ntok: int, heads: int) -> torch.Tensor:
+    """``mhada_vit_batch_attn_split3``: ``vit_batch_attn`` of fp32 qkv [L][ntok][3C] with the result as its three
+    bf16 planes [3][L * ntok][C] (bit-identical to ``split3_rows`` of the fp32 output), the A operand of
+    ``linear_split3``.  head_dim 64 and L <= 8; other shapes raise."""
+    _need_gpu(qkv)
+    if qkv.dtype != torch.float32 or not qkv.is_contiguous():
+        raise ValueError("vit_batch_attn_split3 needs contiguous float32 qkv")
+    C = qkv.shape[-1] // 3
+    planes = torch.empty(3, L * ntok, C, device=qkv.device, dtype=torch.bfloat16)
+    _call("mhada_vit_batch_attn_split3", qkv, qkv.data_ptr(), planes.data_ptr(), L * ntok * C, L, ntok, heads,
+          C // heads)
+    return planes
 
 
 def pos_embed(pos: torch.Tensor, oh: int, ow: int) -> torch.Tensor:
@@ -791,6 +815,22 @@ def attn_split3(q, img, Ns: int, fcs, fcs_mu, fcs_rstd, v_mu) -> torch.Tensor:
     _call("mhada_attn_split3", q, q.data_ptr(), img.data_ptr(), fcs.data_ptr(), fcs_mu.data_ptr(),
           fcs_rstd.data_ptr(), v_mu.data_ptr(), out.data_ptr(), B, H, Nc, Ns)
     return out
+
+
+def attn_split3_planes(q, img, Ns: int, fcs, fcs_mu, fcs_rstd, v_mu) -> torch.Tensor:
+    """``mhada_attn_split3_planes``: ``attn_split3``'s output as its three bf16 planes [3][B * Nc][64 H]
+    (bit-identical to ``split3_rows`` of it), the A operand of the out_conv ``linear_split3``."""
+    _need_gpu(q, img, fcs, fcs_mu, fcs_rstd, v_mu)
+    B, H, Nc, _ = q.shape
+    ldt = (Ns + 63) // 64 * 64
+    if q.dtype != torch.float32 or not q.is_contiguous() or img.dtype != torch.bfloat16 \
+            or img.shape != (B, H, 576 * ldt):
+        raise ValueError(f"attn_split3_planes: q must be contiguous fp32 and img bf16 [B][H][576*{ldt}], got "
+                         f"{q.dtype} / {tuple(img.shape)}")
+    planes = torch.empty(3, B * Nc, H * 64, device=q.device, dtype=torch.bfloat16)
+    _call("mhada_attn_split3_planes", q, q.data_ptr(), img.data_ptr(), fcs.data_ptr(), fcs_mu.data_ptr(),
+          fcs_rstd.data_ptr(), v_mu.data_ptr(), planes.data_ptr(), B, H, Nc, Ns)
+    return planes
 
 
 def _rows64(*ts: torch.Tensor) -> None:

@@ -1,7 +1,7 @@
 """Same-process A/B of the headline inference step (bench.py configs[1]: vit_c, vit_s, adaFormer at
 512^2 batch 8, fp32) under module-flag variants, interleaved rounds, median ms per step.
 
-    python tools/infer_flags_ab.py "base:" "oproj32:ops.F32_SPLIT_OUTPROJ=0" [--rounds 7 --steps 10]
+    python tools/infer_flags_ab.py "base:" "outproj_f32:ops.F32_SPLIT_OUTPROJ=0" [--rounds 7 --steps 10]
 A variant is name:mod.FLAG=int,... with mod one of ops, engine (mhada_hip modules).
 """
 import argparse
