@@ -258,6 +258,31 @@ int mhada_split3_rows(const float* x, void* planes, long long n, mhada_stream_t 
  * 64-column chunk the planes q1 | q0 | q2 | q0 | q1 | q0 (q0 = bf16(x), q1 = bf16(x - q0),
  * q2 = bf16(x - q0 - q1)).  K0 % 64 == 0. */
 int mhada_split3_weight(const float* w, void* out, int N, int K0, int transposed, mhada_stream_t stream);
+
+/* ---- HALF2: an fp32 product as three fp16 products (csrc/gemm_impl.h gemm_h2_kernel) -----------
+ * For GEMMs whose A is a LayerNorm output (|y| <= sqrt(cols) max|gamma| + max|beta|, known from the
+ * parameters) and whose W is a prepared weight: both operands are scaled by exact powers of two into
+ * the fp16 range and split into two fp16 planes hi = fp16(v), lo = fp16(v - hi) (round to nearest,
+ * subnormal plane values flushed to zero); the GEMM sums A_lo W_hi + A_hi W_hi + A_hi W_lo in fp32
+ * accumulators on the fp16 MFMA — half the MFMA work of MHADA_A_SPLIT3 — and multiplies column n by
+ * col_scale[n] = 1 / (s_a t_n).
+ * Added to ABI 18 WITHOUT a version bump, for the reasons given for the _hd entries below: the three
+ * entries are purely additive (mhada_gemm_args keeps its size and layout) and are found by symbol. */
+/* mhada_layernorm with the result as two fp16 planes [2][rows][cols] of scale * y (scale a positive
+ * power of two chosen by the caller so that |scale * y| <= 32768). */
+int mhada_layernorm_half2(const float* x, void* y, const float* gamma, const float* beta, int rows, int cols,
+                          float eps, float scale, mhada_stream_t stream);
+/* W fp32 [N][K0] (K0 % 64 == 0) -> out fp16 [N][2 K0], per 64-column chunk the planes hi | lo of
+ * t[n] w[n][k], and t fp32 [N]: t[n] = 2^(14 - floor(log2 max_k |w[n][k]|)), 1 for a zero or
+ * non-finite row. */
+int mhada_half2_weight(const float* w, void* out, float* t, int N, int K0, mhada_stream_t stream);
+/* C = act(col_scale[n] (A W^T) + bias) + R from those operands: a = fp16 planes [2][M][lda], w = fp16
+ * [N][ldw] (ldw >= 2 K), K = K0, a_mode MHADA_A_ROWS; compute and a_dtype are not read.  Epilogues as
+ * MHADA_A_SPLIT3: bias, relu 0 | 1, residual, fp32 / bf16 C, c2 (bf16 copy, or with c2_planes the
+ * three bf16 planes [3][M][ldc2] of the fp32 result, C may then be NULL).  Refused with
+ * MHADA_ERR_ARG: K % 64 != 0, nb1 * nb2 != 1, a_mu / vt, relu = 2, more than 2^31 tiles, operand
+ * planes beyond 32-bit element offsets, misaligned operands. */
+int mhada_gemm_half2(const mhada_gemm_args* args, const float* col_scale, mhada_stream_t stream);
 /* The block's K|V' projection written straight as that plane image (the engine's fp32 softmax path:
  * replaces mhada_gemm with the vt epilogue plus mhada_split3_kv, adaDecoder.py:178,182):
  *   Y[n][o] = sum_c (fs[b][n][64h+c] - mu_s[b][64h+c]) wkv[b][h][o][c] + bkv[h][o]  (fp32 MFMA),

@@ -1492,6 +1492,238 @@ __global__ void __launch_bounds__(512) gemm_s3_kernel(const GemmP p, int total) 
 }
 
 // ------------------------------------------------------------------------------------
+// HALF2 form of gemm_s3_kernel (mhada_gemm_half2): an fp32 product as THREE fp16 products instead of
+// six bf16 ones, for operands whose magnitude is bounded ahead of time (a LayerNorm output times a
+// prepared weight).  A is two fp16 planes [2][M][lda] of s_a x (hi = fp16(s_a x), lo = fp16(s_a x - hi):
+// 11 + 11 significant bits), W the [N][2 K0] interleave (per 64-column chunk kk the blocks hi | lo of
+// t_n w[n]), both scaled by exact powers of two so every plane value is a normal fp16 number or zero;
+// cs[n] = 1 / (s_a t_n) undoes the scales per output column.  Per chunk the ONE accumulator set takes
+//     lo hi -> hi hi -> hi lo        (A plane x W plane; lo lo <= 2^-22 |x w| is dropped)
+// and the lo planes carry their true magnitude (unscaled relative to hi), so the three terms add as they
+// are.  Same 256x256 tile, wave layout, phases, swizzle, xcd_remap, persistent loop with the lazy store
+// drain and epilogues (the bf16 three-plane c2 output included) as gemm_s3_kernel; what differs:
+//   * v_mfma_f32_32x32x16_f16, three K-tiles per chunk, four 32-KiB stagings (A lo, A hi, W hi, W lo);
+//   * the slots are static: A lo = A slot 0, A hi = A slot 1, W hi = W slot 0, W lo = W slot 1;
+//   * the epilogue multiplies column n by cs[n] (a power of two: exact) before the bias, the ReLU and
+//     the residual;
+//   * no rinit: the residual and the bias would have to be preloaded divided by cs[n]; the two GEMMs
+//     that take this form (QKV, MLP1) have no residual, so a residual is added in the epilogue.
+// Per chunk c:
+//   t  term    reads A/W slot  phases 0,1 stage W        phase 3 stages A        may stay in flight
+//   0  lo hi   0 / 0           lo(c)   -> W slot 1       lo(c+1) -> A slot 0     W lo, A lo' (8 pieces)
+//   1  hi hi   1 / 0           -                         -                       A lo' (4)
+//   2  hi lo   1 / 1           hi(c+1) -> W slot 0       hi(c+1) -> A slot 1     A hi' (4)
+// An A slot is refilled in phase 3 of the last K-tile that reads it and a W slot in phases 0/1 of the
+// K-tile after its last read, as in gemm_s3_kernel.  vmcnt retires in order, so each wait is "everything
+// but the newest n pieces": t0 must see A hi(c) (staged in t2 of the chunk before, older than W lo and
+// A lo'), t1 must see W lo(c) (older than A lo'), t2 must see A lo' and W hi' (older than A hi').  A lo'
+// and W lo have two K-tiles of lead, A hi' and W hi' the one K-tile gemm_ppp_kernel gives all of A.
+// Without a next chunk (the last chunk of the workgroup's last tile) nothing of c + 1 is staged and the
+// waits are 4 (W lo), 0, 0.  Chunk c + 1 may be the next output tile's first chunk: its A hi' and W hi'
+// are older than the epilogue's stores, so the first wait of a tile may leave those in flight too.
+// ------------------------------------------------------------------------------------
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+
+template <typename TO>
+__global__ void __launch_bounds__(512) gemm_h2_kernel(const GemmP p, int total, const float* __restrict__ cs) {
+  constexpr int BK = 64, PE = 512, HALF = 128 * BK, SLOT = 2 * HALF;  // fp16 elements
+  constexpr int SCR = 8 * 4096 / 2;
+  __shared__ __attribute__((aligned(16))) _Float16 smem[4 * SLOT + SCR];  // 160 KiB, the only LDS object
+  _Float16* const smA = smem;
+  _Float16* const smW = smem + 2 * SLOT;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int grp = wave >> 2, wc = wave & 3;
+  const int h = lane >> 5, r32 = lane & 31;
+  const int G = gridDim.x;
+
+  int cofs[2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i) cofs[i] = 8 * ((lane & 7) ^ (4 * i + (lane >> 4)));
+  // per-tile staging state (rows 16*wave + 8i + (lane>>3) of each 128-row half); one problem (nz = 1)
+  struct St {
+    unsigned aoff[2][2], woff[2][2];
+    int m0, n0;
+  };
+  const _Float16* const ab = reinterpret_cast<const _Float16*>(p.a);
+  const _Float16* const wb = reinterpret_cast<const _Float16*>(p.w);
+  auto setup = [&](int w, St& s) {
+    const int t = xcd_remap(w, total);
+    const int tm = t / p.tiles_n, tn = t - tm * p.tiles_n;
+    s.m0 = tm * 256;
+    s.n0 = tn * 256;
+#pragma unroll
+    for (int hh = 0; hh < 2; ++hh)
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        const int rr = 16 * wave + 8 * i + (lane >> 3);
+        const int m = min(s.m0 + 128 * hh + rr, p.M - 1);
+        const int n = min(s.n0 + 128 * hh + rr, p.N - 1);
+        s.woff[hh][i] = (unsigned)((long long)n * p.ldw + cofs[i]);
+        s.aoff[hh][i] = (unsigned)((long long)m * p.lda + cofs[i]);
+      }
+  };
+  // plane `pl` (0: hi, 1: lo) of A, columns 64 kk .. 64 kk + 63, both row halves (4 pieces per wave)
+  auto stage_a = [&](const St& s, int pl, int kk, int slot) {
+    const _Float16* src = ab + pl * p.spl + kk * BK;
+    _Float16* dst = smA + slot * SLOT + wave * 2 * PE;
+#pragma unroll
+    for (int hh = 0; hh < 2; ++hh)
+#pragma unroll
+      for (int i = 0; i < 2; ++i) glds16(src + s.aoff[hh][i], dst + hh * HALF + PE * i);
+  };
+  // block `blk` (0: hi, 1: lo) of chunk kk of the weight interleave, row half hh (2 pieces)
+  auto stage_w = [&](const St& s, int hh, int blk, int kk, int slot) {
+    const _Float16* src = wb + (2 * kk + blk) * BK;
+    _Float16* dst = smW + slot * SLOT + hh * HALF + wave * 2 * PE;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) glds16(src + s.woff[hh][i], dst + PE * i);
+  };
+
+  // fragment reads as gemm_ppp_kernel (16-bit): k-step ks takes chunk 2ks + h at slot (2ks + h) ^ swz
+  const int swz = (r32 >> 1) & 7;
+  int koff[4];
+#pragma unroll
+  for (int ks = 0; ks < 4; ++ks) koff[ks] = 8 * ((2 * ks + h) ^ swz);
+  const _Float16* sA = smA + grp * HALF + r32 * BK;
+  const _Float16* sW = smW + (wc >> 1) * HALF + ((wc & 1) * 64 + r32) * BK;
+  f16x8 af[4][2], wf[2][2];
+  auto read_a = [&](int kp, int slot) {
+#pragma unroll
+    for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+      for (int s2 = 0; s2 < 2; ++s2)
+        af[mt][s2] = *reinterpret_cast<const f16x8*>(sA + slot * SLOT + mt * 32 * BK + koff[2 * kp + s2]);
+  };
+  auto read_w = [&](int nt, int kp, int slot) {
+#pragma unroll
+    for (int s2 = 0; s2 < 2; ++s2)
+      wf[nt][s2] = *reinterpret_cast<const f16x8*>(sW + slot * SLOT + nt * 32 * BK + koff[2 * kp + s2]);
+  };
+  f32x16 acc[4][2];
+  auto zero_acc = [&]() {
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+#pragma unroll
+      for (int b = 0; b < 2; ++b)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc[a][b][e] = 0.f;
+  };
+  // acc[mt][nt][4g+e] <-> column n0 + 64 wc + 32 nt + 8g + 4h + e: undo the operand scales
+  auto scale_acc = [&](const St& s) {
+#pragma unroll
+    for (int nt = 0; nt < 2; ++nt)
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const int n = s.n0 + wc * 64 + nt * 32 + 8 * g + 4 * h;
+        f32x4 c4 = {0.f, 0.f, 0.f, 0.f};
+        if (n + 3 < p.N) {
+          c4 = *reinterpret_cast<const f32x4*>(cs + n);
+        } else {
+#pragma unroll
+          for (int e = 0; e < 4; ++e)
+            if (n + e < p.N) c4[e] = cs[n + e];
+        }
+#pragma unroll
+        for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+          for (int e = 0; e < 4; ++e) acc[mt][nt][4 * g + e] *= c4[e];
+      }
+  };
+  auto compute = [&](int nt) {
+    __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+    for (int s2 = 0; s2 < 2; ++s2)
+#pragma unroll
+      for (int mt = 0; mt < 4; ++mt)
+        acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wf[nt][s2], af[mt][s2], acc[mt][nt], 0, 0, 0);
+    __builtin_amdgcn_s_setprio(0);
+  };
+  // a full tile's epilogue issues at least this many stores per wave
+  constexpr int EPI_MIN = sizeof(TO) == 4 ? 32 : 16;
+  auto wait_vm = [&](int keep) __attribute__((always_inline)) {
+    if (keep == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    else if (keep == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+    else if (keep == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+    else asm volatile("s_waitcnt vmcnt(%0)" :: "n"(8 + EPI_MIN) : "memory");
+  };
+  // one K-tile on A slot as / W slot ws.  sw: stage W block wblk of chunk wkk of tile wt into W slot
+  // wsl (phases 0 and 1); sa: stage A plane apl of chunk akk of tile at into A slot asl (phase 3);
+  // keep: the wave's newest pieces that may stay in flight past this K-tile.
+  auto ktile = [&](int as, int ws, bool sw, const St& wt, int wblk, int wkk, int wsl, bool sa, const St& at, int apl,
+                   int akk, int asl, int keep) __attribute__((always_inline)) {
+    // phase 0
+    read_a(0, as); read_w(0, 0, ws);
+    if (sw) stage_w(wt, 0, wblk, wkk, wsl);
+    PP_LGKM0(); PP_BARRIER(); compute(0); PP_BARRIER();
+    // phase 1
+    read_w(1, 0, ws);
+    if (sw) stage_w(wt, 1, wblk, wkk, wsl);
+    PP_LGKM0(); PP_BARRIER(); compute(1); PP_BARRIER();
+    // phase 2
+    read_a(1, as); read_w(0, 1, ws);
+    PP_LGKM0(); PP_BARRIER(); compute(0); PP_BARRIER();
+    // phase 3
+    read_w(1, 1, ws);
+    if (sa) stage_a(at, apl, akk, asl);
+    wait_vm(keep);
+    PP_LGKM0(); PP_BARRIER(); compute(1); PP_BARRIER();
+  };
+  // chunk kk of tile sc; the lookahead reaches chunk kn of tile sn (nx: there is one).  The two call
+  // sites bind sn to `cur` or `nxt` at compile time (a runtime choice made hipcc copy the state).
+  // wx: the tile's first wait may leave EPI_MIN stores of the previous epilogue in flight.
+  auto chunk = [&](const St& sc, int kk, const St& sn, int kn, bool nx, bool wx) __attribute__((always_inline)) {
+    ktile(0, 0, true, sc, 1, kk, 1, nx, sn, 1, kn, 0, nx ? (wx ? 8 + EPI_MIN : 8) : 4);  // lo hi
+    ktile(1, 0, false, sc, 0, 0, 0, false, sc, 0, 0, 0, nx ? 4 : 0);                     // hi hi
+    ktile(1, 1, nx, sn, 0, kn, 0, nx, sn, 0, kn, 1, nx ? 4 : 0);                         // hi lo
+  };
+
+  const int KC = p.K / BK;
+  int w = blockIdx.x;
+  St cur, nxt;
+  setup(w, cur);
+  bool has_nxt = w + G < total;
+  if (has_nxt) setup(w + G, nxt);
+  zero_acc();
+  stage_a(cur, 1, 0, 0);
+  stage_w(cur, 0, 0, 0, 0); stage_w(cur, 1, 0, 0, 0);
+  stage_a(cur, 0, 0, 1);
+  asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+  PP_BARRIER();
+  if (grp == 1) PP_BARRIER();  // group 1 runs one barrier behind
+
+  bool lazy = false;  // the previous tile's epilogue stores may still be in flight
+  while (true) {
+    for (int kk = 0; kk + 1 < KC; ++kk) chunk(cur, kk, cur, kk + 1, true, kk == 0 && lazy);
+    chunk(cur, KC - 1, nxt, 0, has_nxt, KC == 1 && lazy);
+    // tile boundary: re-align the groups so both store in the same interval, then re-stagger
+    if (grp == 0) PP_BARRIER();
+    // a full tile's stores need not drain before the next tile's first wait
+    lazy = has_nxt && cur.m0 + 256 <= p.M && cur.n0 + 256 <= p.N;
+    __builtin_amdgcn_sched_barrier(0);
+    scale_acc(cur);
+    if (p.lds_epi) {
+      float* scr = reinterpret_cast<float*>(smem + 4 * SLOT) + wave * 1024;
+      bool wide = false;  // (a bf16 residual takes the 8-B form: see gemm_ppp_kernel)
+      if constexpr (sizeof(TO) == 2) {
+        wide = !p.r;
+        if (wide) store_tile_lds_bf16<4>(p, acc, 0, 0, cur.m0 + grp * 128, cur.n0 + wc * 64, lane, scr);
+      }
+      if (!wide) store_tile_lds<TO, 4, 2, true>(p, acc, 0, 0, cur.m0 + grp * 128, cur.n0 + wc * 64, lane, scr);
+    } else {
+      store_tile<TO, 4, 2>(p, acc, 0, 0, cur.m0 + grp * 128 + r32, cur.n0 + wc * 64, h);
+    }
+    if (!has_nxt) break;
+    if (grp == 1) PP_BARRIER();
+    zero_acc();
+    cur = nxt;
+    w += G;
+    has_nxt = w + G < total;
+    if (has_nxt) setup(w + G, nxt);
+  }
+}
+
+// ------------------------------------------------------------------------------------
 // fp32 GEMM for N <= 64 columns over long K (the attention backward's dQ = dS K: M = Nc, K = Ns,
 // one problem per (batch, head); the grouped per-head 1x1 convs).  Streaming A is the whole
 // cost: at the fp32 MFMA rate a 128x64 tile consumes 8 B/clk/CU of A, ~5 TB/s chip-wide, so the
@@ -1638,6 +1870,21 @@ static int launch_gemm_pp(const GemmP& p0, int nz, hipStream_t stream) {
     return check_launch("mhada_gemm");
   }
   return fail("mhada_gemm: no ping-pong form");
+}
+
+// mhada_gemm_half2 (gemm_half2.hip): p.K = K0, p.spl set by the caller, one problem
+template <typename TO>
+static int launch_gemm_h2(const GemmP& p0, const float* cs, hipStream_t stream) {
+  GemmP p = p0;
+  p.tiles_n = (int)(((long long)p.N + 255) / 256);
+  const long long total = (((long long)p.M + 255) / 256) * p.tiles_n;
+  if (total >= (1LL << 31)) return fail("mhada_gemm_half2: more than 2^31 tiles");
+  p.ntiles = (int)total;
+  p.lds_epi = tuning().gemm_ldsepi ? 1 : 0;
+  p.rinit = 0;
+  const int grid = (int)std::min<long long>(total, num_cus());
+  hipLaunchKernelGGL((gemm_h2_kernel<TO>), dim3(grid), dim3(512), 0, stream, p, (int)total, cs);
+  return check_launch("mhada_gemm_half2");
 }
 
 // The ping-pong kernel takes bf16 A (rows or 3x3 taps) with K % 64 == 0, N > 128 and operand

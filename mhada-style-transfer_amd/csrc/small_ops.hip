@@ -12,10 +12,21 @@ namespace mhada {
 // LayerNorm (vit.py:54-55): one wave per row, VPL = cols/64 values per lane, two-pass in
 // registers (mean, then centred sum of squares) — biased variance as nn.LayerNorm.
 // ---------------------------------------------------------------------------------------
-template <typename TO, int VPL, bool SPLIT = false>
+typedef _Float16 f16;
+// an fp16 plane value of the HALF2 operands: round to nearest, a subnormal result flushed to zero (the
+// HALF2 GEMM does not rely on the MFMA keeping fp16 subnormals)
+MHADA_DEV f16 half2_plane(float v) {
+  const f16 q = (f16)v;
+  return fabsf((float)q) < 6.103515625e-05f ? (f16)0.0f : q;
+}
+
+// FORM: 0 = y in TO; 1 (MHADA_BF16X3) = three bf16 planes; 2 (mhada_layernorm_half2) = two fp16 planes of
+// scale * y, scale a power of two (the other forms ignore it).
+template <typename TO, int VPL, int FORM = 0>
 __global__ void __launch_bounds__(256) layernorm_kernel(const float* __restrict__ x, TO* __restrict__ y,
                                                         const float* __restrict__ g,
-                                                        const float* __restrict__ b, int rows, float eps) {
+                                                        const float* __restrict__ b, int rows, float eps,
+                                                        float scale) {
   constexpr int COLS = VPL * 64;
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -26,6 +37,38 @@ __global__ void __launch_bounds__(256) layernorm_kernel(const float* __restrict_
   for (int i = 0; i < VPL / 4; ++i) {
     const f32x4 t = *reinterpret_cast<const f32x4*>(xr + (i * 64 + lane) * 4);
     v[4 * i] = t[0]; v[4 * i + 1] = t[1]; v[4 * i + 2] = t[2]; v[4 * i + 3] = t[3];
+  }
+  if constexpr (FORM == 2) {
+    // The fp32 LayerNorm with its roundings pinned (no implicit contraction, the two fused steps
+    // written out), so the planes are those of the fp32 form's output bit for bit: the fp32
+    // instantiation at cols = 512 rounds mean, v - mean and its square, fuses sum / COLS + eps and
+    // t * gamma + beta.  Then the two fp16 planes of scale * y.
+#pragma clang fp contract(off)
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < VPL; ++i) s += v[i];
+    const float mean = wave_sum(s) * (1.0f / COLS);
+    float ss = 0.f;
+#pragma unroll
+    for (int i = 0; i < VPL; ++i) {
+      v[i] = v[i] - mean;
+      ss += v[i] * v[i];
+    }
+    const float rstd = rsqrtf(fmaf(wave_sum(ss), 1.0f / COLS, eps));
+    TO* yr = y + (long long)row * COLS;
+    const long long plane = (long long)rows * COLS;
+#pragma unroll
+    for (int i = 0; i < VPL / 4; ++i) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int c = (i * 64 + lane) * 4 + e;
+        const float sv = fmaf(v[4 * i + e] * rstd, g[c], b[c]) * scale;
+        const f16 hi = half2_plane(sv);
+        yr[c] = hi;
+        yr[plane + c] = half2_plane(sv - (float)hi);
+      }
+    }
+    return;
   }
   float s = 0.f;
 #pragma unroll
@@ -46,7 +89,7 @@ __global__ void __launch_bounds__(256) layernorm_kernel(const float* __restrict_
     for (int e = 0; e < 4; ++e) {
       const int c = (i * 64 + lane) * 4 + e;
       const float val = (v[4 * i + e] - mean) * rstd * g[c] + b[c];
-      if constexpr (SPLIT) {  // three bf16 planes: val = p0 + p1 + p2 to 2^-25 (the SPLIT3 GEMM operand)
+      if constexpr (FORM == 1) {  // three bf16 planes: val = p0 + p1 + p2 to 2^-25 (the SPLIT3 GEMM operand)
         const bf16 p0 = (bf16)val;
         const float r1 = val - (float)p0;
         const bf16 p1 = (bf16)r1;
@@ -878,9 +921,73 @@ __global__ void __launch_bounds__(256) split3_weight_kernel(const float* __restr
   o[320] = q0;
 }
 
+// The HALF2 GEMM's W operand (ops.half2_weight's layout and rounding): one workgroup per row n of W
+// [N][K0].  t_n = 2^(14 - floor(log2 max_k |w[n][k]|)) (1 for a zero or non-finite row), the planes
+// hi = fp16(t_n w), lo = fp16(t_n w - hi) at out[n][128 (k / 64) + k % 64] and + 64, t_n at t[n].
+__global__ void __launch_bounds__(256) half2_weight_kernel(const float* __restrict__ w, f16* __restrict__ out,
+                                                           float* __restrict__ t, int K0) {
+  __shared__ float red[4];
+  const int n = blockIdx.x;
+  const float* wr = w + (long long)n * K0;
+  float m = 0.f;
+  for (int k = threadIdx.x; k < K0; k += 256) {
+    const float a = fabsf(wr[k]);
+    m = a != a ? INFINITY : fmaxf(m, a);
+  }
+  m = wave_max(m);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
+  __syncthreads();
+  m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+  float tn = 1.f;
+  if (m > 0.f && m < INFINITY) {
+    int e;
+    (void)frexpf(m, &e);  // m = f 2^e, f in [0.5, 1): floor(log2 m) = e - 1
+    tn = ldexpf(1.f, min(15 - e, 127));
+  }
+  if (threadIdx.x == 0) t[n] = tn;
+  f16* o = out + (long long)n * 2 * K0;
+  for (int k = threadIdx.x; k < K0; k += 256) {
+    const float v = wr[k] * tn;
+    const f16 hi = half2_plane(v);
+    o[128 * (k >> 6) + (k & 63)] = hi;
+    o[128 * (k >> 6) + 64 + (k & 63)] = half2_plane(v - (float)hi);
+  }
+}
+
 }  // namespace mhada
 
 using namespace mhada;
+
+extern "C" int mhada_half2_weight(const float* w, void* out, float* t, int N, int K0, mhada_stream_t s_) {
+  if (!w || !out || !t || N <= 0 || K0 <= 0 || K0 % 64) return fail("mhada_half2_weight: bad args (K0 % 64 == 0)");
+  hipLaunchKernelGGL(half2_weight_kernel, dim3((unsigned)N), dim3(256), 0, (hipStream_t)s_, w, (f16*)out, t, K0);
+  return check_launch("mhada_half2_weight");
+}
+
+extern "C" int mhada_layernorm_half2(const float* x, void* y, const float* gamma, const float* beta, int rows,
+                                     int cols, float eps, float scale, mhada_stream_t s_) {
+  hipStream_t s = (hipStream_t)s_;
+  if (!x || !y || !gamma || !beta || rows < 0 || !(scale > 0.f) || !(scale < INFINITY))
+    return fail("mhada_layernorm_half2: bad args");
+  if (rows == 0) return MHADA_OK;
+  if (!aligned16(x)) return fail("mhada_layernorm_half2: x must be 16-byte aligned");
+  const dim3 grid((rows + 3) / 4), blk(256);
+#define LN_CASE(VPL)                                                                                       \
+  case VPL * 64:                                                                                           \
+    hipLaunchKernelGGL((layernorm_kernel<f16, VPL, 2>), grid, blk, 0, s, x, (f16*)y, gamma, beta, rows, eps, \
+                       scale);                                                                             \
+    break;
+  switch (cols) {
+    LN_CASE(4)
+    LN_CASE(8)
+    LN_CASE(16)
+    LN_CASE(32)
+    default:
+      return fail("mhada_layernorm_half2: cols must be 256, 512, 1024 or 2048");
+  }
+#undef LN_CASE
+  return check_launch("mhada_layernorm_half2");
+}
 
 extern "C" int mhada_split3_weight(const float* w, void* out, int N, int K0, int transposed, mhada_stream_t s_) {
   if (!w || !out || N <= 0 || K0 <= 0 || K0 % 64) return fail("mhada_split3_weight: bad args (K0 % 64 == 0)");
@@ -901,11 +1008,11 @@ extern "C" int mhada_layernorm(const float* x, void* y, int y_dtype, const float
 #define LN_CASE(VPL)                                                                                   \
   case VPL * 64:                                                                                       \
     if (y_dtype == MHADA_F32)                                                                          \
-      hipLaunchKernelGGL((layernorm_kernel<float, VPL>), grid, blk, 0, s, x, (float*)y, gamma, beta, rows, eps); \
+      hipLaunchKernelGGL((layernorm_kernel<float, VPL>), grid, blk, 0, s, x, (float*)y, gamma, beta, rows, eps, 1.f); \
     else if (y_dtype == MHADA_BF16X3)                                                                  \
-      hipLaunchKernelGGL((layernorm_kernel<bf16, VPL, true>), grid, blk, 0, s, x, (bf16*)y, gamma, beta, rows, eps); \
+      hipLaunchKernelGGL((layernorm_kernel<bf16, VPL, 1>), grid, blk, 0, s, x, (bf16*)y, gamma, beta, rows, eps, 1.f); \
     else                                                                                               \
-      hipLaunchKernelGGL((layernorm_kernel<bf16, VPL>), grid, blk, 0, s, x, (bf16*)y, gamma, beta, rows, eps); \
+      hipLaunchKernelGGL((layernorm_kernel<bf16, VPL>), grid, blk, 0, s, x, (bf16*)y, gamma, beta, rows, eps, 1.f); \
     break;
   switch (cols) {
     LN_CASE(4)

@@ -174,6 +174,18 @@ def _w6(L: dict, key: str) -> torch.Tensor:
     return L[k6]
 
 
+def _h2(L: dict, ln: str, key: str) -> Optional[dict]:
+    """The HALF2 form of the linear layer `key` fed by LayerNorm `ln` (ops.half2_prepare), decided and built
+    once per prepared layer; None: ops.F32_HALF2 is off or the preparation refused (the layer keeps SPLIT3)."""
+    if not ops.F32_HALF2:
+        return None
+    k2 = key + "_half2"
+    if k2 not in L:
+        with torch.no_grad():
+            L[k2] = ops.half2_prepare(L[ln + "_g"], L[ln + "_b"], L[key])
+    return L[k2]
+
+
 def vit_forward(vit, x: torch.Tensor) -> List[torch.Tensor]:
     """VisionTransformer.forward (vit.py:148-169) on the HIP path."""
     require_device(x, "VisionTransformer")
@@ -202,7 +214,12 @@ def vit_forward(vit, x: torch.Tensor) -> List[torch.Tensor]:
         # cover more CUs than 6x-longer SPLIT3 tiles would)
         split = dt == torch.float32 and _split3_fills(B * N, 3 * C, xs.device)
         split_mlp = dt == torch.float32 and _split3_fills(B * N, C, xs.device)
-        if split:
+        h2q = _h2(L, "ln1", "w_qkv") if split else None
+        h2m = _h2(L, "ln2", "w1") if split_mlp else None
+        if h2q is not None:  # HALF2: three fp16 products where SPLIT3 takes six bf16 ones
+            qkv = ops.linear_half2(ops.layernorm_half2(xs, L["ln1_g"], L["ln1_b"], L["eps"], h2q["s_a"]),
+                                   h2q["w2"], h2q["cs"], L["b_qkv"], dt)
+        elif split:
             qkv = ops.linear_split3(ops.layernorm_split3(xs, L["ln1_g"], L["ln1_b"], L["eps"]), _w6(L, "w_qkv"),
                                     L["b_qkv"], dt)
         else:
@@ -215,9 +232,13 @@ def vit_forward(vit, x: torch.Tensor) -> List[torch.Tensor]:
         else:
             att = ops.vit_batch_attn(qkv.view(B, N, 3 * C), B, N, L["heads"])
             xs = ops.linear(att.view(B * N, C), L["w_o"], L["b_o"], torch.float32, residual=xs)
-        if split_mlp:  # MLP1 writes its ReLU output as planes, MLP2 consumes them (SPLIT3 both)
-            m1 = ops.linear_split3(ops.layernorm_split3(xs, L["ln2_g"], L["ln2_b"], L["eps"]), _w6(L, "w1"),
-                                   L["b1"], dt, relu=True, out_planes=True)
+        if split_mlp:  # MLP1 writes its ReLU output as planes, MLP2 consumes them (SPLIT3; MLP1 HALF2 where prepared)
+            if h2m is not None:
+                m1 = ops.linear_half2(ops.layernorm_half2(xs, L["ln2_g"], L["ln2_b"], L["eps"], h2m["s_a"]),
+                                      h2m["w2"], h2m["cs"], L["b1"], dt, relu=True, out_planes=True)
+            else:
+                m1 = ops.linear_split3(ops.layernorm_split3(xs, L["ln2_g"], L["ln2_b"], L["eps"]), _w6(L, "w1"),
+                                       L["b1"], dt, relu=True, out_planes=True)
             xs = ops.linear_split3(m1, _w6(L, "w2"), L["b2"], torch.float32, residual=xs)
         else:
             h2 = ops.layernorm(xs, L["ln2_g"], L["ln2_b"], dt, L["eps"])

@@ -10,6 +10,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes
+import math
 from typing import Optional
 
 import torch
@@ -62,12 +63,16 @@ def gemm(*, a: torch.Tensor, w: torch.Tensor, c: torch.Tensor, M: int, N: int, K
          r: Optional[torch.Tensor] = None, ldr: int = 0, sr=(0, 0),
          ldc: int = 0, sc=(0, 0), relu: bool = False, pad: int = 0,
          c2: Optional[torch.Tensor] = None, ldc2: int = 0, sc2=(0, 0),
-         vt: Optional[torch.Tensor] = None, ldt: int = 0, svt=(0, 0), c2_planes: bool = False) -> torch.Tensor:
+         vt: Optional[torch.Tensor] = None, ldt: int = 0, svt=(0, 0), c2_planes: bool = False,
+         col_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``mhada_gemm``: C[z] = act(A[z] W[z]^T + bias[z]) + R[z]; strides in elements.  Optional
     c2 (a bf16 copy of an fp32 C; ``c2_planes``: C's three bf16 planes [3][M][ldc2], the next
     SPLIT3 GEMM's operand, with C None = not written) and vt (the transposed V' image of the
-    K|V' projection)."""
-    _need_gpu(a, w, c, a_mu, bias, r, c2, vt)
+    K|V' projection).  ``col_scale`` (fp32 [N]): ``mhada_gemm_half2`` on fp16 HALF2 operands instead."""
+    _need_gpu(a, w, c, a_mu, bias, r, c2, vt, col_scale)
+    half2 = col_scale is not None
+    if half2 and (a.dtype != torch.float16 or col_scale.dtype != torch.float32 or col_scale.numel() < N):
+        raise ValueError("col_scale (fp32 [N]) goes with fp16 HALF2 operands")
     if c is None and not c2_planes:
         raise ValueError("gemm: C may be None only with c2_planes")
     if c2 is not None and (c2.dtype != torch.bfloat16 or (c is not None and c.dtype != torch.float32)):
@@ -86,9 +91,9 @@ def gemm(*, a: torch.Tensor, w: torch.Tensor, c: torch.Tensor, M: int, N: int, K
     args = GemmArgs()
     args.M, args.N, args.K = M, N, K
     args.nb1, args.nb2 = nb
-    args.compute = dt_code(compute)
+    args.compute = BF16 if half2 else dt_code(compute)  # (mhada_gemm_half2 reads neither dtype)
     args.a_mode = a_mode
-    args.a, args.a_dtype, args.lda = a.data_ptr(), dt_code(a.dtype), lda
+    args.a, args.a_dtype, args.lda = a.data_ptr(), BF16 if half2 else dt_code(a.dtype), lda
     args.sa1, args.sa2 = sa
     args.a_mu = _ptr(a_mu)
     args.smu1, args.smu2 = smu
@@ -110,7 +115,10 @@ def gemm(*, a: torch.Tensor, w: torch.Tensor, c: torch.Tensor, M: int, N: int, K
     args.vt, args.ldt = _ptr(vt), ldt
     args.svt1, args.svt2 = svt
     args.c2_planes = int(c2_planes)
-    _call("mhada_gemm", a, ctypes.byref(args))
+    if half2:
+        _call("mhada_gemm_half2", a, ctypes.byref(args), col_scale.data_ptr())
+    else:
+        _call("mhada_gemm", a, ctypes.byref(args))
     return c if c is not None else c2
 
 
@@ -453,6 +461,117 @@ def linear_split3(planes: torch.Tensor, w6: torch.Tensor, bias: Optional[torch.T
              ldw=6 * K0, bias=bias, r=residual, ldr=N if residual is not None else 0, ldc=N, relu=relu,
              c2=c2, ldc2=N if both else 0, c2_planes=both)
     return (c, c2) if both else c
+
+
+# The LayerNorm-fed fp32 GEMMs (the ViT's QKV and MLP1) as HALF2 products instead of SPLIT3: three fp16
+# products of two-plane operands where SPLIT3 takes six bf16 products of three-plane operands.  fp16
+# lacks range, so both operands are scaled by exact powers of two chosen from bounds that do not depend
+# on the data: |LayerNorm(x)| <= sqrt(C) max|gamma| + max|beta|, and the weight rows are known.  False:
+# SPLIT3, with the same kernels and launches as before this switch existed.
+F32_HALF2 = True
+
+_H2_MIN = 2.0 ** -14  # smallest normal fp16: the plane writers flush what is below
+_H2_SCALE_WINDOW = (2.0 ** -40, 2.0 ** 40)
+
+
+def _half2_planes(v: torch.Tensor):
+    """fp32 v -> (hi, lo) fp16: hi = fp16_rn(v), lo = fp16_rn(v - hi), subnormal plane values flushed to zero."""
+    hi = v.half()
+    hi = torch.where(hi.abs() < _H2_MIN, torch.zeros_like(hi), hi)
+    lo = (v - hi.float()).half()
+    lo = torch.where(lo.abs() < _H2_MIN, torch.zeros_like(lo), lo)
+    return hi, lo
+
+
+def half2_a_scale(gamma: torch.Tensor, beta: torch.Tensor) -> Optional[float]:
+    """s_a = 2^floor(log2(32768 / Y)) for a LayerNorm with these parameters, Y = sqrt(C) max|gamma| +
+    max|beta| >= |y|; None where Y is zero or not finite or s_a leaves [2^-40, 2^40] (the layer keeps SPLIT3)."""
+    Y = math.sqrt(gamma.numel()) * float(gamma.detach().abs().max()) + float(beta.detach().abs().max())
+    if not math.isfinite(Y) or Y <= 0.0:
+        return None
+    q = 32768.0 / Y
+    if not math.isfinite(q) or q <= 0.0:
+        return None
+    s_a = 2.0 ** (math.frexp(q)[1] - 1)
+    return s_a if _H2_SCALE_WINDOW[0] <= s_a <= _H2_SCALE_WINDOW[1] else None
+
+
+def half2_weight(w: torch.Tensor):
+    """An fp32 weight [N][K0] (K0 % 64 == 0) as the HALF2 GEMM's W operand -> (w2, t): per row n the scale
+    t_n = 2^(14 - floor(log2 max_k |w_nk|)) (1 for a zero or non-finite row, at most 2^127), the planes hi | lo of t_n w
+    interleaved per 64-column chunk -> w2 fp16 [N][2 K0], and t fp32 [N]."""
+    w = w.float()
+    N, K0 = w.shape
+    if K0 % 64:
+        raise ValueError("half2_weight: K0 must be a multiple of 64")
+    m = w.abs().amax(dim=1)
+    ok = torch.isfinite(m) & (m > 0)
+    e = torch.frexp(torch.where(ok, m, torch.ones_like(m)))[1]  # m = f 2^e, f in [0.5, 1)
+    # 2^min(15 - e, 127) built from its bits (torch.ldexp goes through pow, inexact on the device)
+    t = ((127 + torch.clamp(15 - e, max=127)).to(torch.int32) << 23).view(torch.float32)
+    t = torch.where(ok, t, torch.ones_like(m))
+    hi, lo = _half2_planes(w * t[:, None])
+    w2 = torch.stack([p.view(N, K0 // 64, 64) for p in (hi, lo)], dim=2)
+    return w2.reshape(N, 2 * K0).contiguous(), t
+
+
+def half2_weight_dev(w: torch.Tensor):
+    """``mhada_half2_weight``: half2_weight(w) in one device launch, bit-identical to it."""
+    _need_gpu(w)
+    if w.dtype != torch.float32 or not w.is_contiguous() or w.dim() != 2 or w.shape[1] % 64:
+        raise ValueError("half2_weight_dev needs a contiguous float32 [N][K0] matrix, K0 % 64 == 0")
+    N, K0 = w.shape
+    w2 = torch.empty(N, 2 * K0, device=w.device, dtype=torch.float16)
+    t = torch.empty(N, device=w.device, dtype=torch.float32)
+    _call("mhada_half2_weight", w, w.data_ptr(), w2.data_ptr(), t.data_ptr(), N, K0)
+    return w2, t
+
+
+def half2_prepare(gamma: torch.Tensor, beta: torch.Tensor, w: torch.Tensor) -> Optional[dict]:
+    """The HALF2 form of one LayerNorm-fed linear layer, decided once at preparation time: dict(s_a, w2,
+    cs) with cs[n] = 1 / (s_a t_n), or None — the layer keeps SPLIT3 — where Y is zero or not finite, a
+    weight row is not finite, or a scale leaves [2^-40, 2^40]."""
+    s_a = half2_a_scale(gamma, beta)
+    if s_a is None or w.shape[1] % 64 or not bool(torch.isfinite(w).all()):
+        return None
+    w2, t = half2_weight_dev(w.float().contiguous()) if w.is_cuda else half2_weight(w)
+    lo, hi = _H2_SCALE_WINDOW
+    if float(t.min()) < lo or float(t.max()) > hi:
+        return None
+    return dict(s_a=s_a, w2=w2, cs=(1.0 / (s_a * t.double())).float().contiguous())
+
+
+def layernorm_half2(x: torch.Tensor, g: torch.Tensor, b: torch.Tensor, eps: float, s_a: float) -> torch.Tensor:
+    """``mhada_layernorm_half2``: the fp32 LayerNorm of x, times the power of two s_a, as two fp16 planes
+    [2][rows][cols] (hi, lo), the A operand of ``linear_half2``."""
+    _need_gpu(x, g, b)
+    rows, cols = x.shape
+    y = torch.empty(2, rows, cols, device=x.device, dtype=torch.float16)
+    _call("mhada_layernorm_half2", x, x.data_ptr(), y.data_ptr(), g.data_ptr(), b.data_ptr(), rows, cols, eps, s_a)
+    return y
+
+
+def linear_half2(planes: torch.Tensor, w2: torch.Tensor, cs: torch.Tensor, bias: Optional[torch.Tensor],
+                 out_dtype: torch.dtype, residual: Optional[torch.Tensor] = None, relu: bool = False,
+                 out_planes: bool = False):
+    """fp32-accurate x @ w^T (+bias, relu, residual) from ``layernorm_half2`` planes [2][M][K0],
+    ``half2_weight(w)`` [N][2 K0] and cs [N]: A_lo W_hi + A_hi W_hi + A_hi W_lo in fp32 accumulators on the
+    fp16 MFMA, column n times cs[n] (mhada_gemm_half2).  ``out_planes``: the fp32 result as its three
+    bf16 planes [3][M][N] (the next SPLIT3 GEMM's operand) instead of an fp32 [M][N]."""
+    if planes.dim() != 3 or planes.shape[0] != 2 or planes.dtype != torch.float16 or not planes.is_contiguous():
+        raise ValueError("linear_half2: planes must be contiguous fp16 [2][M][K0]")
+    _, M, K0 = planes.shape
+    N = w2.shape[0]
+    if w2.dtype != torch.float16 or w2.shape[1] != 2 * K0 or not w2.is_contiguous():
+        raise ValueError("linear_half2: w2 must be half2_weight(w), fp16 [N][2*K0]")
+    kw = dict(a=planes, w=w2, M=M, N=N, K=K0, compute=torch.float16, lda=K0, ldw=2 * K0, bias=bias, r=residual,
+              ldr=N if residual is not None else 0, ldc=N, relu=relu, col_scale=cs)
+    if out_planes:
+        if out_dtype != torch.float32:
+            raise ValueError("linear_half2: out_planes splits an fp32 result")
+        c2 = torch.empty(3, M, N, device=planes.device, dtype=torch.bfloat16)
+        return gemm(c=None, c2=c2, ldc2=N, c2_planes=True, **kw)
+    return gemm(c=torch.empty(M, N, device=planes.device, dtype=out_dtype), **kw)
 
 
 def vit_batch_attn(qkv: torch.Tensor, L: int, ntok: int, heads: int, groups: int = 1) -> torch.Tensor:
