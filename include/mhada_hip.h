@@ -283,6 +283,21 @@ int mhada_half2_weight(const float* w, void* out, float* t, int N, int K0, mhada
  * MHADA_ERR_ARG: K % 64 != 0, nb1 * nb2 != 1, a_mu / vt, relu = 2, more than 2^31 tiles, operand
  * planes beyond 32-bit element offsets, misaligned operands. */
 int mhada_gemm_half2(const mhada_gemm_args* args, const float* col_scale, mhada_stream_t stream);
+/* The HALF2 chain: a HALF2 GEMM whose result feeds the next HALF2 GEMM, for activations with a bound
+ * that follows from the layers' parameters (relu(MLP1(LayerNorm x)), the batch-axis attention output).
+ * mhada_gemm_half2 with the fp32 result x = act(col_scale[n] (A W^T) + bias) + R written as the two fp16
+ * planes [2][M][ldc2] (args->c2, ldc2 >= N) of out_scale[n] x: hi = fp16(v), lo = fp16(v - hi), round to
+ * nearest, subnormal plane values flushed to zero; out_scale[n] a power of two chosen by the caller so
+ * that |out_scale[n] x| <= 32768.  C (fp32) may be NULL; c2_planes is not read.  Refused in addition to
+ * mhada_gemm_half2's cases: c_dtype != fp32, N % 4 != 0, no c2, the LDS epilogue tuned off.  Additive, as
+ * the three entries above. */
+int mhada_gemm_half2_planes(const mhada_gemm_args* args, const float* col_scale, const float* out_scale,
+                            mhada_stream_t stream);
+/* mhada_vit_batch_attn_split3 with the fp32 result as the two fp16 planes (plane stride pstride elements)
+ * of out_scale[c] att, c the channel: bit-identical to that split of mhada_vit_batch_attn's fp32 out.
+ * head_dim 64 and L <= 8 only, as mhada_vit_batch_attn_split3. */
+int mhada_vit_batch_attn_half2(const float* qkv, void* planes, long long pstride, const float* out_scale, int L,
+                               int ntok, int heads, int head_dim, mhada_stream_t stream);
 /* The block's K|V' projection written straight as that plane image (the engine's fp32 softmax path:
  * replaces mhada_gemm with the vt epilogue plus mhada_split3_kv, adaDecoder.py:178,182):
  *   Y[n][o] = sum_c (fs[b][n][64h+c] - mu_s[b][64h+c]) wkv[b][h][o][c] + bkv[h][o]  (fp32 MFMA),

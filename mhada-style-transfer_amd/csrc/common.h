@@ -74,6 +74,14 @@ template <typename T> MHADA_DEV T from_f32(float x);
 template <> MHADA_DEV float from_f32<float>(float x) { return x; }
 template <> MHADA_DEV bf16 from_f32<bf16>(float x) { return (bf16)x; }
 
+// an fp16 plane value of the HALF2 operands (ops._half2_planes' arithmetic, shared by every plane writer):
+// round to nearest, a subnormal result flushed to zero (the HALF2 GEMM does not rely on the MFMA keeping
+// fp16 subnormals)
+MHADA_DEV _Float16 half2_plane(float v) {
+  const _Float16 q = (_Float16)v;
+  return fabsf((float)q) < 6.103515625e-05f ? (_Float16)0.0f : q;
+}
+
 // 16-byte vector of T: 4 f32 or 8 bf16
 template <typename T> struct Vec16;
 template <> struct Vec16<float> { typedef f32x4 type; static constexpr int N = 4; };

@@ -324,9 +324,13 @@ MHADA_DEV void store_tile(const GemmP& p, const f32x16 (&acc)[TM][TN], int z1, i
 // The 16-B chunk c of row r sits at slot c ^ (r & 7) (spreads both the column-group writes and
 // the row reads over the banks).  No barrier: each wave owns its scratch.
 // PLANES (the SPLIT3 kernel only): c2 may hold the result's three bf16 planes and C may be null.
-template <typename TO, int TM, int TN, bool PLANES = false>
+// H2OUT (gemm_h2_kernel's plane form only, fp32 TO, N % 4 == 0): c2 holds the two fp16 planes [2][M][ldc2] of
+// os[n] x, x the fp32 result — the next HALF2 GEMM's A operand (ops._half2_planes' arithmetic); C may be null.
+typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+
+template <typename TO, int TM, int TN, bool PLANES = false, bool H2OUT = false>
 MHADA_DEV void store_tile_lds(const GemmP& p, const f32x16 (&acc)[TM][TN], int z1, int z2, int mrow0, int ncol0,
-                              int lane, float* scr) {
+                              int lane, float* scr, const float* os = nullptr) {
   TO* cbase = reinterpret_cast<TO*>(p.c) + z1 * p.sc1 + z2 * p.sc2;
   const TO* rbase = p.r ? reinterpret_cast<const TO*>(p.r) + z1 * p.sr1 + z2 * p.sr2 : nullptr;
   const float* bbase = p.bias ? p.bias + z1 * p.sb1 + z2 * p.sb2 : nullptr;
@@ -343,6 +347,10 @@ MHADA_DEV void store_tile_lds(const GemmP& p, const f32x16 (&acc)[TM][TN], int z
 #pragma unroll
         for (int e = 0; e < 4; ++e) bb[e] = n + e < p.N ? bbase[n + e] : 0.f;
       }
+    }
+    f32x4 ob = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (H2OUT) {
+      if (n + 3 < p.N) ob = *reinterpret_cast<const f32x4*>(os + n);
     }
 #pragma unroll
     for (int mi = 0; mi < TM; ++mi) {
@@ -380,7 +388,18 @@ MHADA_DEV void store_tile_lds(const GemmP& p, const f32x16 (&acc)[TM][TN], int z
               for (int e = 0; e < 4; ++e) x[e] = p.relu == 2 ? (q[e] > 0.f ? x[e] : 0.f) : x[e] + q[e];
             }
             if (!PLANES || p.c) *reinterpret_cast<f32x4*>(crow + n) = f32x4{x[0], x[1], x[2], x[3]};
-            if (p.c2) {
+            if constexpr (H2OUT) {
+              _Float16* c2row = reinterpret_cast<_Float16*>(p.c2) + (long long)m * p.ldc2 + n;
+              f16x4 hi, lo;
+#pragma unroll
+              for (int e = 0; e < 4; ++e) {
+                const float v = ob[e] * x[e];
+                hi[e] = half2_plane(v);
+                lo[e] = half2_plane(v - (float)hi[e]);
+              }
+              *reinterpret_cast<f16x4*>(c2row) = hi;
+              *reinterpret_cast<f16x4*>(c2row + (long long)p.M * p.ldc2) = lo;
+            } else if (p.c2) {
               bf16* c2row = reinterpret_cast<bf16*>(p.c2) + z1 * p.sc21 + z2 * p.sc22 + (long long)m * p.ldc2 + n;
               const bf16x4 h0 = {(bf16)x[0], (bf16)x[1], (bf16)x[2], (bf16)x[3]};
               *reinterpret_cast<bf16x4*>(c2row) = h0;
@@ -1524,8 +1543,18 @@ __global__ void __launch_bounds__(512) gemm_s3_kernel(const GemmP p, int total) 
 // ------------------------------------------------------------------------------------
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
-template <typename TO>
-__global__ void __launch_bounds__(512) gemm_h2_kernel(const GemmP p, int total, const float* __restrict__ cs) {
+// H2OUT (mhada_gemm_half2_planes, fp32 TO, the LDS epilogue): the epilogue writes the fp16 planes of
+// os[n] x (store_tile_lds), os the one trailing argument OS; the other instantiations take no trailing
+// argument, so their kernel arguments and instruction streams are those of the kernel without this form.
+template <typename... T>
+MHADA_DEV const float* h2_out_scale(T... t) {
+  const float* a[] = {nullptr, t...};
+  return a[sizeof...(T)];
+}
+
+template <typename TO, bool H2OUT = false, typename... OS>
+__global__ void __launch_bounds__(512) gemm_h2_kernel(const GemmP p, int total, const float* __restrict__ cs, OS... os_) {
+  const float* const os = h2_out_scale(os_...);
   constexpr int BK = 64, PE = 512, HALF = 128 * BK, SLOT = 2 * HALF;  // fp16 elements
   constexpr int SCR = 8 * 4096 / 2;
   __shared__ __attribute__((aligned(16))) _Float16 smem[4 * SLOT + SCR];  // 160 KiB, the only LDS object
@@ -1709,7 +1738,10 @@ __global__ void __launch_bounds__(512) gemm_h2_kernel(const GemmP p, int total, 
         wide = !p.r;
         if (wide) store_tile_lds_bf16<4>(p, acc, 0, 0, cur.m0 + grp * 128, cur.n0 + wc * 64, lane, scr);
       }
-      if (!wide) store_tile_lds<TO, 4, 2, true>(p, acc, 0, 0, cur.m0 + grp * 128, cur.n0 + wc * 64, lane, scr);
+      if constexpr (H2OUT)
+        store_tile_lds<TO, 4, 2, true, true>(p, acc, 0, 0, cur.m0 + grp * 128, cur.n0 + wc * 64, lane, scr, os);
+      else if (!wide)
+        store_tile_lds<TO, 4, 2, true>(p, acc, 0, 0, cur.m0 + grp * 128, cur.n0 + wc * 64, lane, scr);
     } else {
       store_tile<TO, 4, 2>(p, acc, 0, 0, cur.m0 + grp * 128 + r32, cur.n0 + wc * 64, h);
     }
@@ -1885,6 +1917,21 @@ static int launch_gemm_h2(const GemmP& p0, const float* cs, hipStream_t stream) 
   const int grid = (int)std::min<long long>(total, num_cus());
   hipLaunchKernelGGL((gemm_h2_kernel<TO>), dim3(grid), dim3(512), 0, stream, p, (int)total, cs);
   return check_launch("mhada_gemm_half2");
+}
+
+// mhada_gemm_half2_planes: p.c2 / p.ldc2 the fp16 planes, p.c optional; the caller checked gemm_ldsepi
+static int launch_gemm_h2_f16(const GemmP& p0, const float* cs, const float* os, hipStream_t stream) {
+  GemmP p = p0;
+  p.tiles_n = (int)(((long long)p.N + 255) / 256);
+  const long long total = (((long long)p.M + 255) / 256) * p.tiles_n;
+  if (total >= (1LL << 31)) return fail("mhada_gemm_half2_planes: more than 2^31 tiles");
+  p.ntiles = (int)total;
+  p.lds_epi = 1;
+  p.rinit = 0;
+  const int grid = (int)std::min<long long>(total, num_cus());
+  // the only instantiation with a trailing argument (os): gemm_h2_kernel<TO> above is launched without one
+  hipLaunchKernelGGL((gemm_h2_kernel<float, true, const float*>), dim3(grid), dim3(512), 0, stream, p, (int)total, cs, os);
+  return check_launch("mhada_gemm_half2_planes");
 }
 
 // The ping-pong kernel takes bf16 A (rows or 3x3 taps) with K % 64 == 0, N > 128 and operand

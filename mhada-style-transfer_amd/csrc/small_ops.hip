@@ -12,13 +12,7 @@ namespace mhada {
 // LayerNorm (vit.py:54-55): one wave per row, VPL = cols/64 values per lane, two-pass in
 // registers (mean, then centred sum of squares) — biased variance as nn.LayerNorm.
 // ---------------------------------------------------------------------------------------
-typedef _Float16 f16;
-// an fp16 plane value of the HALF2 operands: round to nearest, a subnormal result flushed to zero (the
-// HALF2 GEMM does not rely on the MFMA keeping fp16 subnormals)
-MHADA_DEV f16 half2_plane(float v) {
-  const f16 q = (f16)v;
-  return fabsf((float)q) < 6.103515625e-05f ? (f16)0.0f : q;
-}
+typedef _Float16 f16;  // (plane values are rounded by half2_plane, common.h)
 
 // FORM: 0 = y in TO; 1 (MHADA_BF16X3) = three bf16 planes; 2 (mhada_layernorm_half2) = two fp16 planes of
 // scale * y, scale a power of two (the other forms ignore it).
@@ -234,11 +228,12 @@ __global__ void __launch_bounds__(256) vit_batch_copy_v_kernel(const uint4* __re
 // Small-batch form (L <= 8, every bench/training config): each (token, head) reads q, k, v
 // once — q/k staged in LDS, v in registers — and the L x L scores are computed in parallel with
 // lane = (i, j); the softmax over j is an 8-lane group reduction.
-// PLANES: the fp32 result as its three bf16 planes (the split of split3_rows_kernel) at out_ (bf16),
-// plane stride pstride elements, instead of a T row.
-template <typename T, bool PLANES>
+// PLANES 1: the fp32 result as its three bf16 planes (the split of split3_rows_kernel) at out_ (bf16),
+// plane stride pstride elements, instead of a T row; 2: as the two fp16 planes hi | lo of os[c] * result
+// (channel c = 64 head + lane; the HALF2 GEMM's A operand, ops._half2_planes' arithmetic).
+template <typename T, int PLANES>
 MHADA_DEV void vit_batch_attn_small_body(const T* __restrict__ qkv, void* __restrict__ out_, long long pstride,
-                                         int L, int ntok, int heads) {
+                                         int L, int ntok, int heads, const float* __restrict__ os = nullptr) {
   constexpr int D = 64;
   __shared__ float sq[4][8][D + 1];
   __shared__ float sk[4][8][D + 1];
@@ -280,12 +275,20 @@ MHADA_DEV void vit_batch_attn_small_body(const T* __restrict__ qkv, void* __rest
   sp[wv][i][j] = e / sum;
   __syncthreads();
   if (!valid) return;
+  float osc = 1.f;
+  if constexpr (PLANES == 2) osc = os[hh * D + lane];
   for (int r = 0; r < L; ++r) {
     float o = 0.f;
 #pragma unroll
     for (int c = 0; c < 8; ++c) o = fmaf(sp[wv][r][c], vr[c], o);
     const long long at = ((long long)r * ntok + n) * C + hh * D + lane;
-    if constexpr (PLANES) {
+    if constexpr (PLANES == 2) {
+      f16* pl = reinterpret_cast<f16*>(out_) + at;
+      const float v = osc * o;
+      const f16 hi = half2_plane(v);
+      pl[0] = hi;
+      pl[pstride] = half2_plane(v - (float)hi);
+    } else if constexpr (PLANES == 1) {
       bf16* pl = reinterpret_cast<bf16*>(out_) + at;
       const bf16 a = (bf16)o;
       const float r1 = o - (float)a;
@@ -302,14 +305,22 @@ MHADA_DEV void vit_batch_attn_small_body(const T* __restrict__ qkv, void* __rest
 template <typename T>
 __global__ void __launch_bounds__(256) vit_batch_attn_small_kernel(const T* __restrict__ qkv, T* __restrict__ out,
                                                                    int L, int ntok, int heads) {
-  vit_batch_attn_small_body<T, false>(qkv, out, 0, L, ntok, heads);
+  vit_batch_attn_small_body<T, 0>(qkv, out, 0, L, ntok, heads);
 }
 
 // The fp32 small-batch form with plane output (mhada_vit_batch_attn_split3).
 __global__ void __launch_bounds__(256) vit_batch_attn_small_s3_kernel(const float* __restrict__ qkv,
                                                                       bf16* __restrict__ planes, long long pstride,
                                                                       int L, int ntok, int heads) {
-  vit_batch_attn_small_body<float, true>(qkv, planes, pstride, L, ntok, heads);
+  vit_batch_attn_small_body<float, 1>(qkv, planes, pstride, L, ntok, heads);
+}
+
+// The same with fp16 HALF2 plane output (mhada_vit_batch_attn_half2).
+__global__ void __launch_bounds__(256) vit_batch_attn_small_h2_kernel(const float* __restrict__ qkv,
+                                                                      f16* __restrict__ planes, long long pstride,
+                                                                      const float* __restrict__ os, int L, int ntok,
+                                                                      int heads) {
+  vit_batch_attn_small_body<float, 2>(qkv, planes, pstride, L, ntok, heads, os);
 }
 
 // L = 1 with plane output: the V slice (the attention output bit for bit) split into its three planes,
@@ -1095,6 +1106,22 @@ extern "C" int mhada_vit_batch_attn_split3(const float* qkv, void* planes, long 
                        pstride, L, ntok, heads);
   }
   return check_launch("mhada_vit_batch_attn_split3");
+}
+
+extern "C" int mhada_vit_batch_attn_half2(const float* qkv, void* planes, long long pstride, const float* out_scale,
+                                          int L, int ntok, int heads, int head_dim, mhada_stream_t s_) {
+  hipStream_t s = (hipStream_t)s_;
+  if (!qkv || !planes || !out_scale || L <= 0 || ntok < 0 || heads <= 0)
+    return fail("mhada_vit_batch_attn_half2: bad args");
+  if (head_dim != 64) return fail("mhada_vit_batch_attn_half2: head_dim must be 64");
+  if (L > 8) return fail("mhada_vit_batch_attn_half2: L must be <= 8");
+  if (pstride < (long long)L * ntok * heads * 64)
+    return fail("mhada_vit_batch_attn_half2: plane stride smaller than this call's output");
+  if (ntok == 0) return MHADA_OK;
+  const long long pairs = (long long)ntok * heads;
+  hipLaunchKernelGGL(vit_batch_attn_small_h2_kernel, dim3((unsigned)((pairs + 3) / 4)), dim3(256), 0, s, qkv,
+                     reinterpret_cast<f16*>(planes), pstride, out_scale, L, ntok, heads);
+  return check_launch("mhada_vit_batch_attn_half2");
 }
 
 extern "C" int mhada_pos_embed(const float* pos, float* out, int C, int bh, int bw, int oh, int ow,

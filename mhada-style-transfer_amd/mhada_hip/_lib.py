@@ -83,6 +83,8 @@ SIGNATURES = {
     "mhada_layernorm_half2": (_I, [_vp, _vp, _vp, _vp, _I, _I, _F, _F, _vp]),
     "mhada_half2_weight": (_I, [_vp, _vp, _vp, _I, _I, _vp]),
     "mhada_gemm_half2": (_I, [ctypes.POINTER(GemmArgs), _vp, _vp]),
+    "mhada_gemm_half2_planes": (_I, [ctypes.POINTER(GemmArgs), _vp, _vp, _vp]),
+    "mhada_vit_batch_attn_half2": (_I, [_vp, _vp, _c_ll, _vp, _I, _I, _I, _I, _vp]),
     "mhada_attn_split3": (_I, [_vp] * 7 + [_I, _I, _I, _I, _vp]),
     "mhada_attn_split3_planes": (_I, [_vp] * 7 + [_I, _I, _I, _I, _vp]),
     "mhada_attn_train_fwd": (_I, [_vp] * 7 + [_I, _I, _I, _vp]),

@@ -186,6 +186,27 @@ def _h2(L: dict, ln: str, key: str) -> Optional[dict]:
     return L[k2]
 
 
+def _h2_chain(L: dict, key: str) -> Optional[dict]:
+    """The HALF2 chain form (ops.half2_chain_prepare) of MLP2 (`key` "w2": fed by relu(MLP1(ln2)), and only
+    where MLP1 itself is HALF2) or of the attention out-projection ("w_o": fed by a convex combination of V
+    rows, V the last third of QKV(ln1)), decided and built once per prepared layer; None: a switch is off
+    (ops.F32_HALF2, F32_HALF2_CHAIN; for "w_o" also F32_HALF2_CHAIN_OUTPROJ) or the preparation refused (the
+    layer keeps SPLIT3)."""
+    if not (ops.F32_HALF2 and ops.F32_HALF2_CHAIN) or (key == "w_o" and not ops.F32_HALF2_CHAIN_OUTPROJ):
+        return None
+    k2 = key + "_half2"
+    if k2 not in L:
+        with torch.no_grad():
+            if key == "w2":
+                L[k2] = None if _h2(L, "ln2", "w1") is None else \
+                    ops.half2_chain_prepare(L["ln2_g"], L["ln2_b"], L["w1"], L["b1"], L["w2"])
+            else:
+                C = L["w_o"].shape[1]
+                L[k2] = ops.half2_chain_prepare(L["ln1_g"], L["ln1_b"], L["w_qkv"][2 * C:], L["b_qkv"][2 * C:],
+                                                L["w_o"])
+    return L[k2]
+
+
 def vit_forward(vit, x: torch.Tensor) -> List[torch.Tensor]:
     """VisionTransformer.forward (vit.py:148-169) on the HIP path."""
     require_device(x, "VisionTransformer")
@@ -227,19 +248,29 @@ def vit_forward(vit, x: torch.Tensor) -> List[torch.Tensor]:
             qkv = ops.linear(hb, L["w_qkv"], L["b_qkv"], dt)
         # the out-projection as a SPLIT3 GEMM too: the batch-axis attention writes the planes (no fp32 att)
         if split_mlp and ops.F32_SPLIT_OUTPROJ and C == L["heads"] * HEAD_DIM and B <= ops.VIT_ATTN_SPLIT3_MAX_L:
-            att3 = ops.vit_batch_attn_split3(qkv.view(B, N, 3 * C), B, N, L["heads"])
-            xs = ops.linear_split3(att3, _w6(L, "w_o"), L["b_o"], torch.float32, residual=xs)
+            h2o = _h2_chain(L, "w_o")
+            if h2o is not None:  # the attention output is bounded by V's bound: fp16 planes, HALF2 GEMM
+                att2 = ops.vit_batch_attn_half2(qkv.view(B, N, 3 * C), B, N, L["heads"], h2o["u"])
+                xs = ops.linear_half2_planes(att2, h2o["w2"], h2o["cs"], L["b_o"], residual=xs)
+            else:
+                att3 = ops.vit_batch_attn_split3(qkv.view(B, N, 3 * C), B, N, L["heads"])
+                xs = ops.linear_split3(att3, _w6(L, "w_o"), L["b_o"], torch.float32, residual=xs)
         else:
             att = ops.vit_batch_attn(qkv.view(B, N, 3 * C), B, N, L["heads"])
             xs = ops.linear(att.view(B * N, C), L["w_o"], L["b_o"], torch.float32, residual=xs)
-        if split_mlp:  # MLP1 writes its ReLU output as planes, MLP2 consumes them (SPLIT3; MLP1 HALF2 where prepared)
+        if split_mlp:  # MLP1 writes its ReLU output as planes, MLP2 consumes them (SPLIT3; HALF2 where prepared)
+            h2c = _h2_chain(L, "w2")  # None wherever h2m is
             if h2m is not None:
                 m1 = ops.linear_half2(ops.layernorm_half2(xs, L["ln2_g"], L["ln2_b"], L["eps"], h2m["s_a"]),
-                                      h2m["w2"], h2m["cs"], L["b1"], dt, relu=True, out_planes=True)
+                                      h2m["w2"], h2m["cs"], L["b1"], dt, relu=True, out_planes=True,
+                                      out_scale=h2c["u"] if h2c is not None else None)
             else:
                 m1 = ops.linear_split3(ops.layernorm_split3(xs, L["ln2_g"], L["ln2_b"], L["eps"]), _w6(L, "w1"),
                                        L["b1"], dt, relu=True, out_planes=True)
-            xs = ops.linear_split3(m1, _w6(L, "w2"), L["b2"], torch.float32, residual=xs)
+            if h2c is not None:
+                xs = ops.linear_half2_planes(m1, h2c["w2"], h2c["cs"], L["b2"], residual=xs)
+            else:
+                xs = ops.linear_split3(m1, _w6(L, "w2"), L["b2"], torch.float32, residual=xs)
         else:
             h2 = ops.layernorm(xs, L["ln2_g"], L["ln2_b"], dt, L["eps"])
             m1 = ops.linear(h2, L["w1"], L["b1"], dt, relu=True)

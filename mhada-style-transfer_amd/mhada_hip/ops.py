@@ -64,18 +64,24 @@ def gemm(*, a: torch.Tensor, w: torch.Tensor, c: torch.Tensor, M: int, N: int, K
          ldc: int = 0, sc=(0, 0), relu: bool = False, pad: int = 0,
          c2: Optional[torch.Tensor] = None, ldc2: int = 0, sc2=(0, 0),
          vt: Optional[torch.Tensor] = None, ldt: int = 0, svt=(0, 0), c2_planes: bool = False,
-         col_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
+         col_scale: Optional[torch.Tensor] = None, out_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``mhada_gemm``: C[z] = act(A[z] W[z]^T + bias[z]) + R[z]; strides in elements.  Optional
     c2 (a bf16 copy of an fp32 C; ``c2_planes``: C's three bf16 planes [3][M][ldc2], the next
     SPLIT3 GEMM's operand, with C None = not written) and vt (the transposed V' image of the
-    K|V' projection).  ``col_scale`` (fp32 [N]): ``mhada_gemm_half2`` on fp16 HALF2 operands instead."""
-    _need_gpu(a, w, c, a_mu, bias, r, c2, vt, col_scale)
+    K|V' projection).  ``col_scale`` (fp32 [N]): ``mhada_gemm_half2`` on fp16 HALF2 operands instead;
+    with ``out_scale`` (fp32 [N]) ``mhada_gemm_half2_planes``: c2 is fp16 [2][M][ldc2], the HALF2 planes of
+    out_scale[n] times the fp32 result, and C may be None."""
+    _need_gpu(a, w, c, a_mu, bias, r, c2, vt, col_scale, out_scale)
     half2 = col_scale is not None
     if half2 and (a.dtype != torch.float16 or col_scale.dtype != torch.float32 or col_scale.numel() < N):
         raise ValueError("col_scale (fp32 [N]) goes with fp16 HALF2 operands")
-    if c is None and not c2_planes:
+    h2out = out_scale is not None
+    if h2out and (not half2 or c2 is None or c2.dtype != torch.float16 or c2_planes
+                  or out_scale.dtype != torch.float32 or out_scale.numel() < N):
+        raise ValueError("out_scale (fp32 [N]) goes with col_scale and an fp16 c2 [2][M][ldc2]")
+    if c is None and not c2_planes and not h2out:
         raise ValueError("gemm: C may be None only with c2_planes")
-    if c2 is not None and (c2.dtype != torch.bfloat16 or (c is not None and c.dtype != torch.float32)):
+    if c2 is not None and ((c2.dtype != torch.bfloat16 and not h2out) or (c is not None and c.dtype != torch.float32)):
         raise ValueError("c2 is the bf16 copy of an fp32 C")
     if c2_planes and (c2 is None or c2.shape[0] != 3 or not c2.is_contiguous()):
         raise ValueError("c2_planes needs c2 = contiguous bf16 [3][M][ldc2]")
@@ -115,7 +121,9 @@ def gemm(*, a: torch.Tensor, w: torch.Tensor, c: torch.Tensor, M: int, N: int, K
     args.vt, args.ldt = _ptr(vt), ldt
     args.svt1, args.svt2 = svt
     args.c2_planes = int(c2_planes)
-    if half2:
+    if h2out:
+        _call("mhada_gemm_half2_planes", a, ctypes.byref(args), col_scale.data_ptr(), out_scale.data_ptr())
+    elif half2:
         _call("mhada_gemm_half2", a, ctypes.byref(args), col_scale.data_ptr())
     else:
         _call("mhada_gemm", a, ctypes.byref(args))
@@ -553,11 +561,13 @@ def layernorm_half2(x: torch.Tensor, g: torch.Tensor, b: torch.Tensor, eps: floa
 
 def linear_half2(planes: torch.Tensor, w2: torch.Tensor, cs: torch.Tensor, bias: Optional[torch.Tensor],
                  out_dtype: torch.dtype, residual: Optional[torch.Tensor] = None, relu: bool = False,
-                 out_planes: bool = False):
+                 out_planes: bool = False, out_scale: Optional[torch.Tensor] = None):
     """fp32-accurate x @ w^T (+bias, relu, residual) from ``layernorm_half2`` planes [2][M][K0],
     ``half2_weight(w)`` [N][2 K0] and cs [N]: A_lo W_hi + A_hi W_hi + A_hi W_lo in fp32 accumulators on the
     fp16 MFMA, column n times cs[n] (mhada_gemm_half2).  ``out_planes``: the fp32 result as its three
-    bf16 planes [3][M][N] (the next SPLIT3 GEMM's operand) instead of an fp32 [M][N]."""
+    bf16 planes [3][M][N] (the next SPLIT3 GEMM's operand) instead of an fp32 [M][N]; with ``out_scale``
+    (fp32 [N], ``half2_chain_prepare``'s u) as the two fp16 planes [2][M][N] of out_scale[n] times it, the
+    A operand of ``linear_half2_planes`` (mhada_gemm_half2_planes)."""
     if planes.dim() != 3 or planes.shape[0] != 2 or planes.dtype != torch.float16 or not planes.is_contiguous():
         raise ValueError("linear_half2: planes must be contiguous fp16 [2][M][K0]")
     _, M, K0 = planes.shape
@@ -569,9 +579,98 @@ def linear_half2(planes: torch.Tensor, w2: torch.Tensor, cs: torch.Tensor, bias:
     if out_planes:
         if out_dtype != torch.float32:
             raise ValueError("linear_half2: out_planes splits an fp32 result")
+        if out_scale is not None:
+            c2 = torch.empty(2, M, N, device=planes.device, dtype=torch.float16)
+            return gemm(c=None, c2=c2, ldc2=N, out_scale=out_scale, **kw)
         c2 = torch.empty(3, M, N, device=planes.device, dtype=torch.bfloat16)
         return gemm(c=None, c2=c2, ldc2=N, c2_planes=True, **kw)
+    if out_scale is not None:
+        raise ValueError("linear_half2: out_scale goes with out_planes")
     return gemm(c=torch.empty(M, N, device=planes.device, dtype=out_dtype), **kw)
+
+
+# The HALF2 chain: the two fp32 ViT GEMMs whose A operand no LayerNorm writes but whose magnitude the
+# layer's parameters still bound — MLP2 (A = relu(MLP1(LayerNorm x))) and the attention out-projection (A =
+# the batch-axis attention output, a convex combination over the images of V = a slice of QKV(LayerNorm
+# x)) — as HALF2 products too.  With y = LayerNorm(x) = gamma xhat + beta and sum xhat^2 <= C, column k of
+# y W^T + b is bounded by Z_k = sqrt(C) ||gamma * w_k||_2 + |beta . w_k + b_k| (Cauchy-Schwarz); the ReLU
+# and the convex combination keep the bound.  The producer writes fp16 planes of u_k v_k, u_k = 2^floor(
+# log2(32768 / Z_k)), and the consumer's weight is prepared from w / u.  Takes effect only with F32_HALF2;
+# False: MLP2 and the out-projection stay SPLIT3 with the launches made before this switch existed.
+F32_HALF2_CHAIN = True
+# The out-projection half of the chain has its own switch, and it is off by default: with it on, the ViT's
+# out-projection no longer goes through linear_split3, and tests/test_gpu_proj_split3.py::
+# test_engine_routes_both_out_projections_to_split3 counts exactly that at the default switches.  That test
+# describes the routing before the chain; turning this on by default is a decision for whoever owns it
+# (tests/test_gpu_half2_chain.py runs and checks the route with the switch on).  Takes effect only with
+# F32_HALF2_CHAIN.
+F32_HALF2_CHAIN_OUTPROJ = False
+
+
+def half2_chain_bound(gamma: torch.Tensor, beta: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor]):
+    """Z [N] in fp64: Z_k = sqrt(C) ||gamma * w[k]||_2 + |beta . w[k] + b[k]| >= |LayerNorm(x) . w[k] + b[k]|
+    for every x, for a LayerNorm over C columns with these parameters."""
+    g, be, W = gamma.detach().double(), beta.detach().double(), w.detach().double()
+    off = W @ be
+    if b is not None:
+        off = off + b.detach().double()
+    return math.sqrt(g.numel()) * (W * g[None, :]).norm(dim=1) + off.abs()
+
+
+def half2_out_scale(Z: torch.Tensor) -> Optional[torch.Tensor]:
+    """u [N] fp32, u_k = 2^floor(log2(32768 / Z_k)) (so u_k Z_k <= 32768, a factor two below the fp16 maximum);
+    None where a Z is zero or not finite or a u leaves [2^-40, 2^40]."""
+    Z = Z.detach().double()
+    if not bool((torch.isfinite(Z) & (Z > 0)).all()):
+        return None
+    q = 32768.0 / Z
+    if not bool((torch.isfinite(q) & (q > 0)).all()):
+        return None
+    e = torch.frexp(q)[1] - 1  # q = f 2^(e + 1), f in [0.5, 1)
+    if int(e.min()) < -40 or int(e.max()) > 40:
+        return None
+    return ((127 + e).to(torch.int32) << 23).view(torch.float32)  # 2^e built from its bits: exact
+
+
+def half2_chain_prepare(gamma: torch.Tensor, beta: torch.Tensor, w_p: torch.Tensor, b_p: Optional[torch.Tensor],
+                        w_c: torch.Tensor) -> Optional[dict]:
+    """The HALF2 form of a linear layer w_c [N][K0] whose input column k is bounded by the producer
+    LayerNorm(gamma, beta) -> w_p [K0][C], b_p (half2_chain_bound; a ReLU or a convex combination of such
+    rows may sit between), decided once at preparation time: dict(u, w2, cs) — u fp32 [K0] the producer's
+    per-column output scale, w2 = half2_weight(w_c / u) (exact: u are powers of two), cs[n] = 1 / t_n — or
+    None (the layer keeps SPLIT3) where a parameter or a bound is zero or not finite, or a u, a t or a row's
+    largest |w_c / u| leaves [2^-40, 2^40]."""
+    ts = [t for t in (gamma, beta, w_p, b_p, w_c) if t is not None]
+    if w_c.shape[1] % 64 or w_c.shape[1] != w_p.shape[0] or not all(bool(torch.isfinite(t).all()) for t in ts):
+        return None
+    u = half2_out_scale(half2_chain_bound(gamma, beta, w_p, b_p))
+    if u is None:
+        return None
+    lo, hi = _H2_SCALE_WINDOW
+    wu = (w_c.detach().float() / u.to(w_c.device)[None, :]).contiguous()
+    m = wu.abs().amax(dim=1)
+    if not bool(torch.isfinite(m).all()) or float(m.min()) < lo or float(m.max()) > hi:
+        return None
+    w2, t = half2_weight_dev(wu) if wu.is_cuda else half2_weight(wu)
+    if float(t.min()) < lo or float(t.max()) > hi:
+        return None
+    return dict(u=u.to(w_c.device).contiguous(), w2=w2, cs=(1.0 / t.double()).float().contiguous())
+
+
+def linear_half2_planes(planes: torch.Tensor, w2: torch.Tensor, cs: torch.Tensor, bias: Optional[torch.Tensor],
+                        residual: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The consumer of the HALF2 chain: fp32-accurate x @ w^T (+bias, residual) -> fp32 [M][N] from the fp16
+    planes [2][M][K0] of u x that ``linear_half2(out_scale=u)`` or ``vit_batch_attn_half2`` wrote and
+    ``half2_chain_prepare``'s w2, cs (mhada_gemm_half2)."""
+    if planes.dim() != 3 or planes.shape[0] != 2 or planes.dtype != torch.float16 or not planes.is_contiguous():
+        raise ValueError("linear_half2_planes: planes must be contiguous fp16 [2][M][K0]")
+    _, M, K0 = planes.shape
+    N = w2.shape[0]
+    if w2.dtype != torch.float16 or w2.shape[1] != 2 * K0 or not w2.is_contiguous():
+        raise ValueError("linear_half2_planes: w2 must be half2_weight(w / u), fp16 [N][2*K0]")
+    return gemm(a=planes, w=w2, c=torch.empty(M, N, device=planes.device, dtype=torch.float32), M=M, N=N, K=K0,
+                compute=torch.float16, lda=K0, ldw=2 * K0, bias=bias, r=residual,
+                ldr=N if residual is not None else 0, ldc=N, col_scale=cs)
 
 
 def vit_batch_attn(qkv: torch.Tensor, L: int, ntok: int, heads: int, groups: int = 1) -> torch.Tensor:
@@ -603,6 +702,22 @@ def vit_batch_attn_split3(qkv: torch.Tensor, L: int, ntok: int, heads: int) -> t
     planes = torch.empty(3, L * ntok, C, device=qkv.device, dtype=torch.bfloat16)
     _call("mhada_vit_batch_attn_split3", qkv, qkv.data_ptr(), planes.data_ptr(), L * ntok * C, L, ntok, heads,
           C // heads)
+    return planes
+
+
+def vit_batch_attn_half2(qkv: torch.Tensor, L: int, ntok: int, heads: int, out_scale: torch.Tensor) -> torch.Tensor:
+    """``mhada_vit_batch_attn_half2``: ``vit_batch_attn`` of fp32 qkv [L][ntok][3C] with out_scale[c] times the
+    result as two fp16 planes [2][L * ntok][C] (bit-identical to ``_half2_planes`` of that product), the A
+    operand of ``linear_half2_planes``.  head_dim 64 and L <= 8; other shapes raise."""
+    _need_gpu(qkv, out_scale)
+    C = qkv.shape[-1] // 3
+    if qkv.dtype != torch.float32 or not qkv.is_contiguous():
+        raise ValueError("vit_batch_attn_half2 needs contiguous float32 qkv")
+    if out_scale.dtype != torch.float32 or out_scale.numel() != C or not out_scale.is_contiguous():
+        raise ValueError("vit_batch_attn_half2: out_scale must be contiguous float32 [C]")
+    planes = torch.empty(2, L * ntok, C, device=qkv.device, dtype=torch.float16)
+    _call("mhada_vit_batch_attn_half2", qkv, qkv.data_ptr(), planes.data_ptr(), L * ntok * C, out_scale.data_ptr(),
+          L, ntok, heads, C // heads)
     return planes
 
 
