@@ -237,6 +237,19 @@ int mhada_attn_hd(const void* q, const void* kv, const float* fcs, const float* 
                   const float* fcs_rstd, const float* v_mu, void* out, int dtype, int B, int H,
                   int D, int Nc, int Ns, int activation, mhada_stream_t stream);
 
+/* ---- head width 512 (additive to ABI 18; csrc/attn_wide.hip) -----------------------------------
+ * The single-head AdaAttN of AdaAttnTransformer (adaDecoder.py:85-131): softmax attention with one
+ * head over all D = 512 channels on the bf16 MFMA, fp32 accumulation and online softmax, A never in
+ * HBM:  out = sqrt(max(A V'^2 - (A V')^2, 1e-6)) * (fcs - fcs_mu) * fcs_rstd + A V' + v_mu,
+ * A = softmax over keys of q . k with q already in log2 units (log2 e folded into the Q projection).
+ * q [B][Nc][512], k [B][Ns][512], v [B][Ns][512] (V', centred over the tokens, no bias) bf16 (`dtype`
+ * must be MHADA_BF16); fcs [B][Nc][512], fcs_mu / fcs_rstd / v_mu [B][512] fp32; out [B][Nc][512] fp32
+ * and, when out16 is not NULL, its bf16 rounding [B][Nc][512].  D must be 512.  All pointers 16-byte
+ * aligned.  Bit-identical from run to run. */
+int mhada_attn_wide(const void* q, const void* k, const void* v, const float* fcs, const float* fcs_mu,
+                    const float* fcs_rstd, const float* v_mu, float* out, void* out16, int dtype, int B,
+                    int Nc, int Ns, int D, mhada_stream_t stream);
+
 /* The fp32 softmax MHAda attention (adaDecoder.py:186-198, mhada_attn's contract and output) as
  * fp32-accurate SPLIT3 products on the bf16 MFMA (ABI 16; csrc/attn_split3.hip): every fp32 operand as
  * three bf16 planes x = x0 + x1 + x2 (round to nearest: x0 = bf16(x), x1 = bf16(x - x0),

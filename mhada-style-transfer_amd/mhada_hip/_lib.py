@@ -76,6 +76,7 @@ SIGNATURES = {
     "mhada_fold_block_hd": (_I, [_vp] * 12 + [_F, _I, _I, _I, _I, _vp]),
     "mhada_cosine_prep_hd": (_I, [_vp, _vp, _I, _I, _I, _I, _I, _I, _vp]),
     "mhada_attn_hd": (_I, [_vp] * 7 + [_I, _I, _I, _I, _I, _I, _I, _vp]),
+    "mhada_attn_wide": (_I, [_vp] * 9 + [_I, _I, _I, _I, _I, _vp]),
     "mhada_split3_kv": (_I, [_vp, _vp, _vp, _I, _I, _I, _vp]),
     "mhada_kv_proj_split3": (_I, [_vp] * 5 + [_I, _I, _I, _vp]),
     "mhada_split3_rows": (_I, [_vp, _vp, _c_ll, _vp]),

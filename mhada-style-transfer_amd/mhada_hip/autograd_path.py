@@ -397,6 +397,34 @@ def adaformer_forward(ada, fc: Sequence[torch.Tensor], fs: Sequence[torch.Tensor
     return fcs, decoder_forward(ada.decoder, fcs)
 
 
+def adaattn_forward(blk, fc: torch.Tensor, fs: torch.Tensor, fcs: torch.Tensor, chunk: int = 4096) -> torch.Tensor:
+    """AdaAttN.forward (adaDecoder.py:102-131), the reference expression with aten ops (CPU tensors and
+    calls that need gradients), query-chunked as ada_attn_for_loss so the Nc x Ns matrix is never whole."""
+    b, _, h, w = fc.shape
+    q = blk.f(F.instance_norm(fc)).reshape(b, -1, h * w).permute(0, 2, 1)
+    k = blk.g(F.instance_norm(fs))
+    k = k.reshape(b, k.shape[1], -1)
+    v = blk.h(fs)
+    v = v.reshape(b, v.shape[1], -1).permute(0, 2, 1)
+    ms, ss = [], []
+    for q0 in range(0, q.shape[1], chunk):
+        a = _softmax_or_cosine(q[:, q0:q0 + chunk], k, blk.activation_name)
+        m = torch.bmm(a, v)
+        ms.append(m)
+        ss.append(torch.sqrt((torch.bmm(a, v * v) - m * m).clamp(min=1e-6)))
+    m = torch.cat(ms, 1).reshape(b, h, w, -1).permute(0, 3, 1, 2)
+    s = torch.cat(ss, 1).reshape(b, h, w, -1).permute(0, 3, 1, 2)
+    return s * F.instance_norm(fcs) + m
+
+
+def adaformer1_forward(ada, fc: Sequence[torch.Tensor], fs: Sequence[torch.Tensor]) -> torch.Tensor:
+    """AdaAttnTransformer.forward (adaDecoder.py:226-232): returns cs."""
+    fcs = fc[0]
+    for i in range(ada.num_layers):
+        fcs = adaattn_forward(ada.adaAttNs[i], fc[i], fs[i], fcs)
+    return decoder_forward(ada.decoder, fcs)
+
+
 def imagenet_normalize(x: torch.Tensor) -> torch.Tensor:
     """imageNet1k_normalize (vgg19.py:6-12)."""
     x = x.float()

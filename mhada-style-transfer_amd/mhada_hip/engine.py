@@ -469,6 +469,87 @@ def _block_forward_hd(blk, fc: _Feat, fs: Optional[_Feat], fcs: _Feat, dt: torch
     return f
 
 
+def adaattn_prep(blk, dtype):
+    """Weights of the single-head AdaAttN (f, g, h: 512 x 512 1x1 convs).  bf16: f carries log2(e) in weight
+    and bias (the attention's log2-unit Q contract); h also in fp32 for v_mu = W_h mu_s + b_h."""
+    def build(dt):
+        def w(m):
+            return m.weight.reshape(m.weight.shape[0], -1).float()
+        qs = ops.LOG2E if dt == torch.bfloat16 else 1.0
+        return dict(wf=(w(blk.f) * qs).to(dt).contiguous(), bf=(blk.f.bias.float() * qs).contiguous(),
+                    wg=w(blk.g).to(dt).contiguous(), bg=blk.g.bias.float().contiguous(),
+                    wh=w(blk.h).to(dt).contiguous(), bh=blk.h.bias.float().contiguous(),
+                    wh32=w(blk.h).contiguous())
+    return cached_prep(blk, dtype, build)
+
+
+def adaattn_forward(blk, fc: _Feat, fs: _Feat, fcs: _Feat, dt: torch.dtype, want_bf16: bool = False) -> _Feat:
+    """AdaAttN.forward (adaDecoder.py:102-131), one head over all 512 channels; returns the fp32 block output
+    [B][Nc][512] as a _Feat.  The projections are ordinary mhada_gemm calls (N = K = 512) fed by
+    ops.rows_normalize output (Q, K: the InstanceNorm is applied to the rows, not folded into per-batch
+    weights) or by fs itself (V).
+
+    fp32 (and cosine in either dtype: there is no bf16 cosine form at this width, so a bf16 cosine block
+    runs this route in fp32): V = h(fs) uncentred, ops.loss_attn at d_qk = d_v = 512 on natural-unit logits;
+    cosine divides the Q and K rows by their L2 norm after the projection.
+    bf16 softmax (ops.BF16_WIDE_ATTN): ops.attn_wide — Q in log2 units (adaattn_prep), V' = h(fs - mean(fs))
+    without bias through the GEMM's a_mu, v_mu = W_h mu_s + b_h added in the attention's epilogue (the 64-wide
+    path's centring).  ``want_bf16``: the attention also writes the bf16 copy (``.t16``) for the decoder."""
+    C = ops.WIDE_WIDTH
+    B, Nc, Cc = fc.t.shape
+    if Cc != C or fs.t.shape[2] != C or fcs.t.shape[2] != C or blk.f.weight.shape[0] != C:
+        raise ValueError(f"the HIP AdaAttN kernels implement qkv_dim {C}, got channels {Cc} / {fs.t.shape[2]} / "
+                         f"{fcs.t.shape[2]} and qkv_dim {blk.f.weight.shape[0]}")
+    if fs.t.shape[0] != B or fcs.t.shape[:2] != (B, Nc):
+        raise ValueError(f"batch / token mismatch: fc {tuple(fc.t.shape)}, fs {tuple(fs.t.shape)}, fcs {tuple(fcs.t.shape)}")
+    Ns = fs.t.shape[1]
+    cosine = blk.activation_name == "cosine"
+    wide = dt == torch.bfloat16 and not cosine and ops.BF16_WIDE_ATTN
+    prep = adaattn_prep(blk, torch.bfloat16 if wide else torch.float32)
+    pdt = torch.bfloat16 if wide else torch.float32
+    mu_c, rstd_c = fc.stats()
+    mu_s, rstd_s = fs.stats()
+    mu_o, rstd_o = fcs.stats()
+    q = ops.linear(ops.rows_normalize(fc.t, mu_c, rstd_c).view(B * Nc, C), prep["wf"], prep["bf"], pdt).view(B, Nc, C)
+    k = ops.linear(ops.rows_normalize(fs.t, mu_s, rstd_s).view(B * Ns, C), prep["wg"], prep["bg"], pdt).view(B, Ns, C)
+    if wide:
+        v = torch.empty(B, Ns, C, device=fs.t.device, dtype=torch.bfloat16)
+        ops.gemm(a=fs.t, w=prep["wh"], c=v, M=Ns, N=C, K=C, compute=torch.bfloat16, lda=C, sa=(Ns * C, 0), nb=(B, 1),
+                 a_mu=mu_s, smu=(C, 0), ldw=C, ldc=C, sc=(Ns * C, 0))
+        v_mu = ops.linear(mu_s, prep["wh32"], prep["bh"], torch.float32)
+        with _timed("mhada_attn"):
+            res = ops.attn_wide(q, k, v, fcs.t, mu_o, rstd_o, v_mu, want_bf16=want_bf16)
+        out, t16 = res if want_bf16 else (res, None)
+    else:
+        v = ops.linear(fs.t.view(B * Ns, C), prep["wh"], prep["bh"], torch.float32).view(B, Ns, C)
+        if cosine:
+            q = q / q.norm(dim=-1, keepdim=True)
+            k = k / k.norm(dim=-1, keepdim=True)
+        with _timed("mhada_attn"):
+            out = ops.loss_attn(q, k, v, fcs.t, mu_o, rstd_o, ACT_COSINE if cosine else ACT_SOFTMAX)
+        t16 = None
+    f = _Feat(out, fc.h, fc.w)
+    f.t16 = t16
+    return f
+
+
+def adaformer1_forward(ada, fc: Sequence[torch.Tensor], fs: Sequence[torch.Tensor]) -> torch.Tensor:
+    """AdaAttnTransformer.forward (adaDecoder.py:226-232): num_layers single-head AdaAttN blocks and the
+    Decoder; returns cs.  No per-style cache (multi-head only)."""
+    require_device(fc[0], "AdaAttnTransformer")
+    dt = resolve_compute_dtype(ada)
+    L = ada.num_layers
+    fcf = [_Feat.from_nchw(t) for t in fc[:L]]
+    fsf = [_Feat.from_nchw(t) for t in fs[:L]]
+    fcs = fcf[0]
+    for i in range(L):
+        fcs = adaattn_forward(ada.adaAttNs[i], fcf[i], fsf[i], fcs, dt,
+                              want_bf16=(dt == torch.bfloat16 and i == L - 1))
+    B, N, C = fcs.t.shape
+    x16 = None if fcs.t16 is None else fcs.t16.view(B, fcs.h, fcs.w, C)
+    return decoder_forward_tokens(ada.decoder, fcs.t.view(B, fcs.h, fcs.w, C), dt, x16=x16)
+
+
 def style_cache(ada, fs: Sequence[torch.Tensor], dt: torch.dtype):
     """Per-style cache of the blocks' style-side tensors (the video path of
     infer_video.py:58-92: fs = vit_s(style) once, adaFormer(fc, fs) per frame).

@@ -995,6 +995,43 @@ def attn_hd(q, kv, fcs, fcs_mu, fcs_rstd, v_mu, activation: int) -> torch.Tensor
     return out
 
 
+WIDE_WIDTH = 512  # the head width of mhada_attn_wide (csrc/attn_wide.hip): one head over all channels
+# bf16 single-head softmax blocks run mhada_attn_wide (measured faster than the fp32 mhada_loss_attn route at
+# this width, tools/attn_wide_ab.py).  False: bf16 blocks take the fp32 route as well.
+BF16_WIDE_ATTN = True
+
+
+def attn_wide(q, k, v, fcs, fcs_mu, fcs_rstd, v_mu, want_bf16: bool = False):
+    """``mhada_attn_wide``: the fused single-head AdaAttN softmax attention at D = 512 on the bf16 MFMA from
+    bf16 q [B][Nc][512] (log2 units), k [B][Ns][512] and v [B][Ns][512] (V', centred, no bias); fcs
+    [B][Nc][512] and fcs_mu / fcs_rstd / v_mu [B][512] fp32.  Returns out [B][Nc][512] fp32, or with
+    ``want_bf16`` the pair (out, its bf16 rounding)."""
+    _need_gpu(q, k, v, fcs, fcs_mu, fcs_rstd, v_mu)
+    if q.dim() != 3 or k.dim() != 3 or v.dim() != 3:
+        raise ValueError(f"attn_wide: needs q [B][Nc][{WIDE_WIDTH}], k and v [B][Ns][{WIDE_WIDTH}], got "
+                         f"{tuple(q.shape)} / {tuple(k.shape)} / {tuple(v.shape)}")
+    B, Nc, D = q.shape
+    Ns = k.shape[1]
+    if D != WIDE_WIDTH:
+        raise ValueError(f"attn_wide: head width must be {WIDE_WIDTH}, got {D}")
+    if k.shape != (B, Ns, D) or v.shape != (B, Ns, D):
+        raise ValueError(f"attn_wide: needs k and v [B][Ns][{D}] matching q, got {tuple(q.shape)} / {tuple(k.shape)} / "
+                         f"{tuple(v.shape)}")
+    for t in (q, k, v):
+        if t.dtype != torch.bfloat16 or not t.is_contiguous():
+            raise ValueError(f"attn_wide: q, k, v must be contiguous bfloat16, got {t.dtype}")
+    if Nc <= 0 or Ns <= 0:
+        raise ValueError(f"attn_wide: needs Nc > 0 and Ns > 0, got {Nc} / {Ns}")
+    for t, shape in ((fcs, (B, Nc, D)), (fcs_mu, (B, D)), (fcs_rstd, (B, D)), (v_mu, (B, D))):
+        if tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError(f"attn_wide: needs contiguous fp32 {shape}, got {tuple(t.shape)} {t.dtype}")
+    out = torch.empty(B, Nc, D, device=q.device, dtype=torch.float32)
+    out16 = torch.empty(B, Nc, D, device=q.device, dtype=torch.bfloat16) if want_bf16 else None
+    _call("mhada_attn_wide", q, q.data_ptr(), k.data_ptr(), v.data_ptr(), fcs.data_ptr(), fcs_mu.data_ptr(),
+          fcs_rstd.data_ptr(), v_mu.data_ptr(), out.data_ptr(), _ptr(out16), BF16, B, Nc, Ns, D)
+    return (out, out16) if want_bf16 else out
+
+
 # The fp32 softmax MHAda attention as SPLIT3 products on the bf16 MFMA (mhada_attn_split3): fp32-accurate
 # (against fp64 at or below the fp32 MFMA kernel's error) and faster.  False: the fp32 MFMA kernel.
 F32_SPLIT_ATTN = True

@@ -7,10 +7,10 @@ state_dict keys; reference checkpoints load with ``load_state_dict(strict=True)`
 Compute dtype: fp32 by default; bf16 under ``torch.autocast("cuda", dtype=torch.bfloat16)``
 or with ``module.compute_dtype = torch.bfloat16``.
 """
-from .adaDecoder import AdaAttnForLoss, AdaAttnMultiHead, AdaAttnTransformerMultiHead
+from .adaDecoder import AdaAttN, AdaAttnForLoss, AdaAttnMultiHead, AdaAttnTransformer, AdaAttnTransformerMultiHead
 from .conv import Decoder
 from .vgg19 import VGG19
 from .vit import VisionTransformer
 
 __all__ = ["VisionTransformer", "AdaAttnTransformerMultiHead", "AdaAttnMultiHead", "AdaAttnForLoss",
-           "Decoder", "VGG19"]
+           "AdaAttnTransformer", "AdaAttN", "Decoder", "VGG19"]

@@ -40,6 +40,32 @@ class AdaAttnForLoss(nn.Module):
         return autograd_path.ada_attn_for_loss(c_x, s_x, c_1x, s_1x, self.activation_name)
 
 
+class AdaAttN(nn.Module):
+    """``adaDecoder.py:85-131``: the learnable single-head AdaAttN, forward(fc, fs, fcs) -> (B, qkv_dim, h, w).
+    1x1 convs ``f``, ``g``, ``h`` and no out_conv (identical state_dict keys; the InstanceNorms and the
+    activation carry no state).  On a ROCm device: ``mhada_hip.engine.adaattn_forward`` (qkv_dim 512 only) —
+    fp32 through mhada_loss_attn at d_qk = d_v = 512, bf16 softmax through mhada_attn_wide; a bf16 cosine
+    block runs the fp32 route.  CPU tensors and calls that need gradients run the aten form."""
+
+    def __init__(self, qkv_dim, activation="softmax"):
+        super().__init__()
+        self.compute_dtype = None
+        self.f = nn.Conv2d(qkv_dim, qkv_dim, 1)
+        self.g = nn.Conv2d(qkv_dim, qkv_dim, 1)
+        self.h = nn.Conv2d(qkv_dim, qkv_dim, 1)
+        self.activation_name = _check_activation(activation)
+
+    def forward(self, fc: torch.Tensor, fs: torch.Tensor, fcs: torch.Tensor):
+        if not fc.is_cuda or autograd_path.needs_grad(self, fc, fs, fcs):  # autograd / CPU tensors
+            return autograd_path.adaattn_forward(self, fc, fs, fcs)
+        dt = engine.resolve_compute_dtype(self)
+        fcf = engine._Feat.from_nchw(fc)
+        fsf = engine._Feat.from_nchw(fs)
+        fcsf = fcf if fcs is fc else engine._Feat.from_nchw(fcs)
+        out = engine.adaattn_forward(self, fcf, fsf, fcsf, dt)
+        return engine.tokens_to_nchw(out.t, out.h, out.w)
+
+
 class AdaAttnMultiHead(nn.Module):
     """``adaDecoder.py:134-206``: forward(fc, fs, fcs) -> (B, qkv_dim, h, w)."""
 
@@ -65,6 +91,24 @@ class AdaAttnMultiHead(nn.Module):
         fcsf = fcf if fcs is fc else engine._Feat.from_nchw(fcs)
         out = engine.block_forward(self, fcf, fsf, fcsf, dt)
         return engine.tokens_to_nchw(out.t, out.h, out.w)
+
+
+class AdaAttnTransformer(nn.Module):
+    """``adaDecoder.py:209-232``: num_layers single-head AdaAttN blocks + Decoder.
+    forward(fc_list, fs_list) -> cs (a tensor; no second calling convention)."""
+
+    def __init__(self, num_layers: int = 3, qkv_dim: int = 512, activation: str = "softmax"):
+        super().__init__()
+        self.num_layers = num_layers
+        self.compute_dtype = None
+        self.adaAttNs = nn.ModuleList([AdaAttN(qkv_dim, activation) for _ in range(num_layers)])
+        self.decoder = Decoder()
+
+    def forward(self, fc: List[torch.Tensor], fs: List[torch.Tensor]) -> torch.Tensor:
+        fc, fs = list(fc), list(fs)
+        if not fc[0].is_cuda or autograd_path.needs_grad(self, *fc, *fs):  # autograd / CPU tensors
+            return autograd_path.adaformer1_forward(self, fc, fs)
+        return engine.adaformer1_forward(self, fc, fs)
 
 
 class AdaAttnTransformerMultiHead(nn.Module):
