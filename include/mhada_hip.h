@@ -480,6 +480,14 @@ int mhada_attn_train_bwd_bf16(const float* q, const float* k, const float* v, co
  * (infer_image.py:86). w fp32 [9][Cin][3] (tap = 3*ky+kx, cin, out); Cin in {32, 64, 128}. */
 int mhada_conv3x3_out3(const void* x, int dtype, const float* w, const float* b, float* y,
                        int B, int H, int W, int Cin, int clamp255, mhada_stream_t stream);
+/* The same layer writing the cv2-ready u8 frame itself (the video path's output, infer_video.py:94,
+ * 110-112): arguments and kernel dispatch as mhada_conv3x3_out3, the output as mhada_frame_emit
+ * writes it (frames u8 [B][H][row_bytes], row_bytes >= 3W, padding bytes untouched).  Bit for bit
+ * mhada_frame_emit(mhada_conv3x3_out3(..., clamp255 = 1)) in every dispatch form; the fp32 frame
+ * never reaches memory. */
+int mhada_conv3x3_out3_u8(const void* x, int dtype, const float* w, const float* b, void* frames,
+                          long long row_bytes, int bgr, int B, int H, int W, int Cin,
+                          mhada_stream_t stream);
 
 /* Bilinear x2 upsample, align_corners=False (ConvReluInterpolate, conv.py:71) on NHWC:
  * x [B][H][W][C] -> y [B][2H][2W][C], dtype fp32|bf16, C % 8 == 0.  Used where the decoder's
@@ -657,6 +665,17 @@ int mhada_rows_normalize(const float* x, const float* mu, const float* rs, float
  * out: [B][3][Ho][Wo] fp32. */
 int mhada_frame_ingest(const void* frames, int B, int H, int W, long long row_bytes, int bgr, float* out,
                        int Ho, int Wo, mhada_stream_t stream);
+/* Frame emit, the inverse (infer_video.py:94,110-112: cs.clamp(0,255) -> permute(1,2,0) -> numpy
+ * astype(uint8) -> cv2.cvtColor(RGB2BGR)).  x: fp32 [B][3][H][W] contiguous, any range, R,G,B planes.
+ * frames: u8 [B][H][row_bytes], pixel (y, x) at bytes 3x..3x+2 of its row, B,G,R when bgr != 0 and
+ * R,G,B otherwise; row_bytes >= 3W, images H * row_bytes apart; bytes 3W..row_bytes-1 of a row are
+ * never written (a padded cv2 Mat keeps its padding).  Only the base pointers' natural alignment
+ * is assumed (any row_bytes, any W).
+ * Per value: fminf(fmaxf(v, 0), 255) then truncation toward zero — what clamp(0,255) followed by
+ * numpy astype(np.uint8) gives for every finite input and +-inf.  NaN gives 0 (fmaxf returns its
+ * non-NaN operand); numpy leaves that case undefined. */
+int mhada_frame_emit(const float* x, int B, int H, int W, void* frames, long long row_bytes, int bgr,
+                     mhada_stream_t stream);
 
 /* fp32 3x3 convolution as Winograd F(2x2,3x3) on the fp32 MFMA (2.25x fewer products than the
  * direct correlation).  Replaces the fp32 Conv2d(k=3) of the decoder (ReflectionPad2d(1) + conv,

@@ -95,6 +95,34 @@ MHADA_DEV float bilerp(float ly0, float ly1, float lx0, float lx1, float x00, fl
   return fmaf(ly1, fmaf(lx0, x10, lx1 * x11), ly0 * fmaf(lx0, x00, lx1 * x01));
 }
 
+// ---- u8 frame output (mhada_frame_emit and the u8 form of the last decoder layer) ---------
+// clamp(0, 255) then numpy's astype(uint8) (truncation toward zero); NaN -> 0 (fmaxf returns the
+// non-NaN operand).
+MHADA_DEV uint32_t emit_u8(float v) { return (uint32_t)fminf(fmaxf(v, 0.f), 255.f); }
+
+// the three bytes of one pixel in memory order (byte 0 lowest): B,G,R for bgr, else R,G,B
+MHADA_DEV uint32_t emit_pack(float r, float g, float b, int bgr) {
+  const uint32_t c0 = emit_u8(bgr ? b : r), c1 = emit_u8(g), c2 = emit_u8(bgr ? r : b);
+  return c0 | (c1 << 8) | (c2 << 16);
+}
+
+// Store one packed pixel per lane.  Called by every lane of the wave, `valid` or not.  `q` = the lane's
+// position in its group of four consecutive lanes, which hold four consecutive pixels of one row
+// when `quad` is set (the same value in all four lanes; implies valid): the 12 bytes then leave as
+// three dword stores from lanes q = 0..2 if the group's first byte is 4-byte aligned.  Everything
+// else (row ends, groups that straddle two rows, misaligned rows) is three byte stores per pixel.
+MHADA_DEV void emit_store_px(uint8_t* p, uint32_t px, int q, bool valid, bool quad) {
+  const uint32_t nx = (uint32_t)__shfl_down((int)px, 1, 64);
+  if (quad && ((uintptr_t)(p - 3 * q) & 3) == 0) {
+    // dword q of the group: bytes 4q .. 4q+3 = the upper 3 - q bytes of this pixel, then the next one's
+    if (q < 3) *reinterpret_cast<uint32_t*>(p + q) = q == 0 ? (px | (nx << 24)) : ((px >> (8 * q)) | (nx << (24 - 8 * q)));
+  } else if (valid) {
+    p[0] = (uint8_t)px;
+    p[1] = (uint8_t)(px >> 8);
+    p[2] = (uint8_t)(px >> 16);
+  }
+}
+
 MHADA_DEV float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

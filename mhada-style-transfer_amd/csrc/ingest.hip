@@ -129,9 +129,72 @@ __global__ void __launch_bounds__(256) frame_ingest_up_kernel(const uint8_t* __r
   o[2 * plane] = (bl / 255.0f) * 255.0f;
 }
 
+// ---------------------------------------------------------------------------------------
+// Frame emit, the inverse of the ingest: the per-frame output conversion of infer_video.py:94,
+// 110-112 (cs.clamp(0, 255) -> permute(1, 2, 0) -> .cpu().numpy().astype(np.uint8) ->
+// cv2.cvtColor(RGB2BGR)) in one HBM-bound pass, fp32 [B][3][H][W] -> u8 [B][H][row_bytes].
+//
+// A workgroup converts one segment of kEmitSeg pixels of one image row.  Lanes read consecutive
+// pixels of each of the three planes (coalesced dwords along W) and put the pixel's three bytes
+// into LDS at byte m + 3 * (pixel - segment start), m = the segment's first output address & 3:
+// LDS dword d is then the aligned global dword at (address - m) + 4d.  After the barrier each lane
+// takes whole LDS dwords: one that lies inside the segment's bytes [m, m + n) leaves as a dword
+// store, the (at most two) that straddle its ends leave as byte stores of the bytes inside — the
+// head and tail of a row whose start or length is no multiple of 4.  Bytes past 3W of a row are
+// never written.
+// ---------------------------------------------------------------------------------------
+constexpr int kEmitSeg = 1024;  // pixels per workgroup: 12 KiB read, 3 KiB written
+
+__global__ void __launch_bounds__(256) frame_emit_kernel(const float* __restrict__ x, uint8_t* __restrict__ out, int H,
+                                                          int W, long long row_bytes, int bgr, int segs) {
+  __shared__ __attribute__((aligned(4))) uint8_t seg[3 * kEmitSeg + 4];
+  const long long blk = blockIdx.x;
+  const int sg = (int)(blk % segs);
+  const long long row = blk / segs;  // b * H + y
+  const long long b = row / H;
+  const int y = (int)(row - b * H);
+  const int xs = sg * kEmitSeg, npx = min(kEmitSeg, W - xs);
+  const long long plane = (long long)H * W;
+  const float* src = x + b * 3 * plane + (long long)y * W + xs;
+  uint8_t* dst = out + row * row_bytes + 3LL * xs;
+  const int m = (int)((uintptr_t)dst & 3);
+  for (int i = threadIdx.x; i < npx; i += 256) {
+    const uint32_t px = emit_pack(src[i], src[plane + i], src[2 * plane + i], bgr);
+    uint8_t* s = seg + m + 3 * i;
+    s[0] = (uint8_t)px;
+    s[1] = (uint8_t)(px >> 8);
+    s[2] = (uint8_t)(px >> 16);
+  }
+  __syncthreads();
+  const int n = 3 * npx;  // the segment's bytes sit at LDS [m, m + n)
+  uint8_t* base = dst - m;  // 4-byte aligned
+  for (int d = threadIdx.x; 4 * d < m + n; d += 256) {
+    const uint32_t v = *reinterpret_cast<const uint32_t*>(seg + 4 * d);
+    if (4 * d >= m && 4 * d + 4 <= m + n) {
+      *reinterpret_cast<uint32_t*>(base + 4 * d) = v;
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (4 * d + k >= m && 4 * d + k < m + n) base[4 * d + k] = (uint8_t)(v >> (8 * k));
+    }
+  }
+}
+
 }  // namespace mhada
 
 using namespace mhada;
+
+extern "C" int mhada_frame_emit(const float* x, int B, int H, int W, void* frames, long long row_bytes, int bgr,
+                                mhada_stream_t s_) {
+  if (!x || !frames || B <= 0 || H <= 0 || W <= 0) return fail("mhada_frame_emit: bad args");
+  if (row_bytes < 3LL * W) return fail("mhada_frame_emit: row_bytes < 3*W");
+  const int segs = (W + kEmitSeg - 1) / kEmitSeg;
+  const long long nb = (long long)B * H * segs;
+  if (nb >= (1LL << 31)) return fail("mhada_frame_emit: grid too large");
+  hipLaunchKernelGGL(frame_emit_kernel, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)s_, x, (uint8_t*)frames, H, W,
+                     row_bytes, bgr != 0, segs);
+  return check_launch("mhada_frame_emit");
+}
 
 extern "C" int mhada_frame_ingest(const void* frames, int B, int H, int W, long long row_bytes, int bgr, float* out,
                                   int Ho, int Wo, mhada_stream_t s_) {

@@ -534,6 +534,15 @@ __global__ void __launch_bounds__(256) rownorm_kernel(T* __restrict__ x, long lo
   r[lane] = from_f32<T>(v / n);
 }
 
+// Output of the last decoder layer's kernels, selected by the type YT of the output pointer (a
+// template parameter of all three):
+//   float:   NCHW fp32 planes y [B][3][H][W] (mhada_conv3x3_out3; row_bytes and bgr unused);
+//   uint8_t: the cv2-ready u8 frame [B][H][row_bytes], pixel (y, x) at bytes 3x..3x+2 of its row in
+//            B,G,R (bgr) or R,G,B order (mhada_conv3x3_out3_u8): the clamp(0,255) and the byte
+//            cast of mhada_frame_emit applied to the values the fp32 form would have stored, so
+//            the fp32 frame never reaches HBM.
+template <typename YT> constexpr bool kOut3U8 = sizeof(YT) == 1;
+
 // ---------------------------------------------------------------------------------------
 // Last decoder layer: ReflectionPad(1) + conv3x3 Cin->3 + bias + ReLU, NHWC in, NCHW fp32 out.
 // One thread per output pixel (adjacent lanes = adjacent pixels, each reading its own
@@ -541,10 +550,10 @@ __global__ void __launch_bounds__(256) rownorm_kernel(T* __restrict__ x, long lo
 // so they are wave-uniform: the compiler fetches them with scalar loads into SGPRs and the
 // FMAs take them as scalar operands (no LDS broadcast traffic).
 // ---------------------------------------------------------------------------------------
-template <typename T, int CIN>
+template <typename T, int CIN, typename YT>
 __global__ void __launch_bounds__(256) conv_out3_kernel(const T* __restrict__ x, const float* __restrict__ w,
-                                                        const float* __restrict__ bias, float* __restrict__ y,
-                                                        int B, int H, int W, int clamp255) {
+                                                        const float* __restrict__ bias, YT* __restrict__ y,
+                                                        int B, int H, int W, int clamp255, long long row_bytes, int bgr) {
   const long long pix = (long long)blockIdx.x * 256 + threadIdx.x;
   if (pix >= (long long)B * H * W) return;
   const int b = (int)(pix / ((long long)H * W));
@@ -573,11 +582,19 @@ __global__ void __launch_bounds__(256) conv_out3_kernel(const T* __restrict__ x,
   }
   a0 = fmaxf(a0, 0.f); a1 = fmaxf(a1, 0.f); a2 = fmaxf(a2, 0.f);
   if (clamp255) { a0 = fminf(a0, 255.f); a1 = fminf(a1, 255.f); a2 = fminf(a2, 255.f); }
-  const long long plane = (long long)H * W;
-  float* yb = y + (long long)b * 3 * plane + (long long)yy * W + xx;
-  yb[0] = a0;
-  yb[plane] = a1;
-  yb[2 * plane] = a2;
+  if constexpr (kOut3U8<YT>) {
+    // lanes pix & 3 = 0..3 hold four consecutive pixels; one row when the first and last are in it
+    // (the last pixel of the group then exists, so no lane of it returned above)
+    const int q = (int)(pix & 3);
+    uint8_t* p = y + ((long long)b * H + yy) * row_bytes + 3LL * xx;
+    emit_store_px(p, emit_pack(a0, a1, a2, bgr), q, true, xx - q >= 0 && xx - q + 3 < W);
+  } else {
+    const long long plane = (long long)H * W;
+    float* yb = y + (long long)b * 3 * plane + (long long)yy * W + xx;
+    yb[0] = a0;
+    yb[plane] = a1;
+    yb[2 * plane] = a2;
+  }
 }
 
 // ---------------------------------------------------------------------------------------
@@ -595,10 +612,11 @@ __global__ void __launch_bounds__(256) conv_out3_kernel(const T* __restrict__ x,
 constexpr int kOut3Rows = 8;    // row tiles per workgroup strip (fp32 kernel)
 constexpr int kOut3RowsM = 16;  // bf16 MFMA kernel: longer strips amortise its weight-fragment prologue
 
-template <int CIN, int CC>
+template <int CIN, int CC, typename YT>
 __global__ void __launch_bounds__(256, 2) conv_out3_mfma_kernel(const bf16* __restrict__ x, const float* __restrict__ w,
-                                                             const float* __restrict__ bias, float* __restrict__ y,
-                                                             int H, int W, int tiles_x, int strips_y, int clamp255) {
+                                                             const float* __restrict__ bias, YT* __restrict__ y,
+                                                             int H, int W, int tiles_x, int strips_y, int clamp255,
+    long long row_bytes, int bgr) {
   // the halo is staged in CC-channel chunks (CC = 32: 31 KiB per buffer, two workgroups per CU;
   // the whole 64-channel halo double-buffered took 114 KiB, one workgroup per CU)
   constexpr int TR = 4, TC = 64, HR = TR + 2, HC = TC + 2, LP = CC + 8, NH = CIN / 32, NCK = CIN / CC;
@@ -701,12 +719,26 @@ __global__ void __launch_bounds__(256, 2) conv_out3_mfma_kernel(const bf16* __re
 #pragma unroll
         for (int g = 0; g < TC / 16; ++g) {
           const int xx = x0 + 16 * g + lane;
-          if (lane < 16 && yy < H && xx < W) {
+          if constexpr (kOut3U8<YT>) {
+            // every lane runs the store helper (its shuffle); lanes 0-15 hold the group's pixels
+            float v[3];
 #pragma unroll
             for (int o = 0; o < 3; ++o) {
-              float v = fmaxf(acc[g][o] + bo[o], 0.f);
-              if (clamp255) v = fminf(v, 255.f);
-              y[(((long long)b * 3 + o) * H + yy) * W + xx] = v;
+              v[o] = fmaxf(acc[g][o] + bo[o], 0.f);
+              if (clamp255) v[o] = fminf(v[o], 255.f);
+            }
+            const bool row = lane < 16 && yy < H;
+            const int xc = min(xx, W - 1);  // lanes past the row compute an in-bounds address, store nothing
+            uint8_t* p = y + ((long long)b * H + min(yy, H - 1)) * row_bytes + 3LL * xc;
+            emit_store_px(p, emit_pack(v[0], v[1], v[2], bgr), lane & 3, row && xx < W, row && (xx | 3) < W);
+          } else {
+            if (lane < 16 && yy < H && xx < W) {
+#pragma unroll
+              for (int o = 0; o < 3; ++o) {
+                float v = fmaxf(acc[g][o] + bo[o], 0.f);
+                if (clamp255) v = fminf(v, 255.f);
+                y[(((long long)b * 3 + o) * H + yy) * W + xx] = v;
+              }
             }
           }
         }
@@ -728,10 +760,11 @@ __global__ void __launch_bounds__(256, 2) conv_out3_mfma_kernel(const bf16* __re
 // load-issue bound: 744 -> 219 us at 512^2 B8 with CC = 16 (63 KiB of LDS, two workgroups per
 // CU; CC = 32: 306 us at one workgroup per CU, CC = 8: 329 us).
 // ---------------------------------------------------------------------------------------
-template <int CIN, int CC>
+template <int CIN, int CC, typename YT>
 __global__ void __launch_bounds__(256) conv_out3_f32_kernel(const float* __restrict__ x, const float* __restrict__ w,
-                                                            const float* __restrict__ bias, float* __restrict__ y,
-                                                            int H, int W, int tiles_x, int strips_y, int clamp255) {
+                                                            const float* __restrict__ bias, YT* __restrict__ y,
+                                                            int H, int W, int tiles_x, int strips_y, int clamp255,
+    long long row_bytes, int bgr) {
   constexpr int TR = 4, TC = 64, HR = TR + 2, HC = TC + 2, LP = CC + 4, NCK = CIN / CC;
   constexpr int Q = CC / 4, NQ = HR * HC * Q, PER = (NQ + 255) / 256;
   __shared__ __attribute__((aligned(16))) float tile[2][HR * HC * LP];
@@ -793,12 +826,23 @@ __global__ void __launch_bounds__(256) conv_out3_f32_kernel(const float* __restr
     }
     if (ck == NCK - 1) {
       const int yy = ys + r * TR + wave, xx = x0 + lane;
-      if (yy < H && xx < W) {
+      if constexpr (kOut3U8<YT>) {
+        // every lane runs the store helper (its shuffle)
         float o[3] = {fmaxf(a0 + bias[0], 0.f), fmaxf(a1 + bias[1], 0.f), fmaxf(a2 + bias[2], 0.f)};
 #pragma unroll
-        for (int k = 0; k < 3; ++k) {
+        for (int k = 0; k < 3; ++k)
           if (clamp255) o[k] = fminf(o[k], 255.f);
-          y[(((long long)b * 3 + k) * H + yy) * W + xx] = o[k];
+        const int xc = min(xx, W - 1);  // lanes past the row compute an in-bounds address, store nothing
+        uint8_t* p = y + ((long long)b * H + min(yy, H - 1)) * row_bytes + 3LL * xc;
+        emit_store_px(p, emit_pack(o[0], o[1], o[2], bgr), lane & 3, yy < H && xx < W, yy < H && (xx | 3) < W);
+      } else {
+        if (yy < H && xx < W) {
+          float o[3] = {fmaxf(a0 + bias[0], 0.f), fmaxf(a1 + bias[1], 0.f), fmaxf(a2 + bias[2], 0.f)};
+#pragma unroll
+          for (int k = 0; k < 3; ++k) {
+            if (clamp255) o[k] = fminf(o[k], 255.f);
+            y[(((long long)b * 3 + k) * H + yy) * W + xx] = o[k];
+          }
         }
       }
       a0 = a1 = a2 = 0.f;
@@ -1201,57 +1245,74 @@ extern "C" int mhada_cosine_prep(void* q, void* kv, int dtype, int B, int H, int
   return check_launch("mhada_cosine_prep");
 }
 
-extern "C" int mhada_conv3x3_out3(const void* x, int dtype, const float* w, const float* b, float* y, int B, int H,
-                                  int W, int Cin, int clamp255, mhada_stream_t s_) {
-  if (!x || !w || !b || !y || B <= 0 || H < 2 || W < 2) return fail("mhada_conv3x3_out3: bad args");
-  if (!aligned16(x)) return fail("mhada_conv3x3_out3: x must be 16-byte aligned");
+// the dispatch shared by mhada_conv3x3_out3 (YT = float) and mhada_conv3x3_out3_u8 (uint8_t)
+template <typename YT>
+static int conv3x3_out3_launch(const char* name, const void* x, int dtype, const float* w, const float* b, YT* y,
+                               long long row_bytes, int bgr, int B, int H, int W, int Cin, int clamp255, hipStream_t s) {
+  const std::string nm(name);
   const long long pix = (long long)B * H * W;
   const dim3 grid((unsigned)((pix + 255) / 256));
-  hipStream_t s = (hipStream_t)s_;
   // bf16, Cin 32/64: the MFMA tile kernel (tuning out3_mfma = 0 selects the per-pixel VALU kernel)
   if (dtype == MHADA_BF16 && tuning().out3_mfma && (Cin == 32 || Cin == 64)) {
     const int tiles_x = (W + 63) / 64, strips_y = (H + 4 * kOut3RowsM - 1) / (4 * kOut3RowsM);
     const long long nb = (long long)B * strips_y * tiles_x;
-    if (nb >= (1LL << 31)) return fail("mhada_conv3x3_out3: grid too large");
+    if (nb >= (1LL << 31)) return fail(nm + ": grid too large");
     const dim3 g((unsigned)nb);
     if (Cin == 64)
-      hipLaunchKernelGGL((conv_out3_mfma_kernel<64, 32>), g, dim3(256), 0, s, (const bf16*)x, w, b, y, H, W, tiles_x, strips_y, clamp255);
+      hipLaunchKernelGGL((conv_out3_mfma_kernel<64, 32, YT>), g, dim3(256), 0, s, (const bf16*)x, w, b, y, H, W, tiles_x, strips_y, clamp255, row_bytes, bgr);
     else
-      hipLaunchKernelGGL((conv_out3_mfma_kernel<32, 32>), g, dim3(256), 0, s, (const bf16*)x, w, b, y, H, W, tiles_x, strips_y, clamp255);
-    return check_launch("mhada_conv3x3_out3");
+      hipLaunchKernelGGL((conv_out3_mfma_kernel<32, 32, YT>), g, dim3(256), 0, s, (const bf16*)x, w, b, y, H, W, tiles_x, strips_y, clamp255, row_bytes, bgr);
+    return check_launch(name);
   }
   // fp32, Cin 32/64: the LDS-tiled kernel (tuning out3_tile = 0 selects the per-pixel kernel)
   if (dtype == MHADA_F32 && tuning().out3_tile && (Cin == 32 || Cin == 64)) {
     const int tiles_x = (W + 63) / 64, strips_y = (H + 4 * kOut3Rows - 1) / (4 * kOut3Rows);
     const long long nb = (long long)B * strips_y * tiles_x;
-    if (nb >= (1LL << 31)) return fail("mhada_conv3x3_out3: grid too large");
+    if (nb >= (1LL << 31)) return fail(nm + ": grid too large");
     const dim3 g((unsigned)nb);
     if (Cin == 64)
-      hipLaunchKernelGGL((conv_out3_f32_kernel<64, 16>), g, dim3(256), 0, s, (const float*)x, w, b, y, H, W, tiles_x,
-                         strips_y, clamp255);
+      hipLaunchKernelGGL((conv_out3_f32_kernel<64, 16, YT>), g, dim3(256), 0, s, (const float*)x, w, b, y, H, W, tiles_x,
+                         strips_y, clamp255, row_bytes, bgr);
     else
-      hipLaunchKernelGGL((conv_out3_f32_kernel<32, 16>), g, dim3(256), 0, s, (const float*)x, w, b, y, H, W, tiles_x,
-                         strips_y, clamp255);
-    return check_launch("mhada_conv3x3_out3");
+      hipLaunchKernelGGL((conv_out3_f32_kernel<32, 16, YT>), g, dim3(256), 0, s, (const float*)x, w, b, y, H, W, tiles_x,
+                         strips_y, clamp255, row_bytes, bgr);
+    return check_launch(name);
   }
 #define OUT3_CASE(CI)                                                                                          \
   case CI:                                                                                                     \
     if (dtype == MHADA_F32)                                                                                    \
-      hipLaunchKernelGGL((conv_out3_kernel<float, CI>), grid, dim3(256), 0, s, (const float*)x, w, b, y, B, H, W, \
-                         clamp255);                                                                            \
+      hipLaunchKernelGGL((conv_out3_kernel<float, CI, YT>), grid, dim3(256), 0, s, (const float*)x, w, b, y, B, H, W, \
+                         clamp255, row_bytes, bgr);                                                            \
     else                                                                                                       \
-      hipLaunchKernelGGL((conv_out3_kernel<bf16, CI>), grid, dim3(256), 0, s, (const bf16*)x, w, b, y, B, H, W,   \
-                         clamp255);                                                                            \
+      hipLaunchKernelGGL((conv_out3_kernel<bf16, CI, YT>), grid, dim3(256), 0, s, (const bf16*)x, w, b, y, B, H, W,   \
+                         clamp255, row_bytes, bgr);                                                            \
     break;
   switch (Cin) {
     OUT3_CASE(64)
     OUT3_CASE(32)
     OUT3_CASE(128)
     default:
-      return fail("mhada_conv3x3_out3: Cin must be 32, 64 or 128");
+      return fail(nm + ": Cin must be 32, 64 or 128");
   }
 #undef OUT3_CASE
-  return check_launch("mhada_conv3x3_out3");
+  return check_launch(name);
+}
+
+extern "C" int mhada_conv3x3_out3(const void* x, int dtype, const float* w, const float* b, float* y, int B, int H,
+                                  int W, int Cin, int clamp255, mhada_stream_t s_) {
+  if (!x || !w || !b || !y || B <= 0 || H < 2 || W < 2) return fail("mhada_conv3x3_out3: bad args");
+  if (!aligned16(x)) return fail("mhada_conv3x3_out3: x must be 16-byte aligned");
+  return conv3x3_out3_launch("mhada_conv3x3_out3", x, dtype, w, b, y, 0LL, 0, B, H, W, Cin, clamp255, (hipStream_t)s_);
+}
+
+extern "C" int mhada_conv3x3_out3_u8(const void* x, int dtype, const float* w, const float* b, void* frames,
+                                     long long row_bytes, int bgr, int B, int H, int W, int Cin, mhada_stream_t s_) {
+  if (!x || !w || !b || !frames || B <= 0 || H < 2 || W < 2) return fail("mhada_conv3x3_out3_u8: bad args");
+  if (!aligned16(x)) return fail("mhada_conv3x3_out3_u8: x must be 16-byte aligned");
+  if (row_bytes < 3LL * W) return fail("mhada_conv3x3_out3_u8: row_bytes < 3*W");
+  // clamp255 = 1: the values cast are those mhada_conv3x3_out3(clamp255 = 1) stores
+  return conv3x3_out3_launch("mhada_conv3x3_out3_u8", x, dtype, w, b, (uint8_t*)frames, row_bytes, bgr != 0, B, H, W,
+                             Cin, 1, (hipStream_t)s_);
 }
 
 // 2 x 2 output blocks for 16-B aligned tensors (round 5): one thread per (source pixel, 8-channel

@@ -111,6 +111,8 @@ SIGNATURES = {
     "mhada_flow_warp_mask": (_I, [_vp, _vp, _vp, _I, _I, _F, _I, _vp]),
     "mhada_warp_l1": (_I, [_vp, _vp, _vp, _vp, _vp, _vp, _I, _I, _I, _I, _vp]),
     "mhada_frame_ingest": (_I, [_vp, _I, _I, _I, _c_ll, _I, _vp, _I, _I, _vp]),
+    "mhada_frame_emit": (_I, [_vp, _I, _I, _I, _vp, _c_ll, _I, _vp]),
+    "mhada_conv3x3_out3_u8": (_I, [_vp, _I, _vp, _vp, _vp, _c_ll, _I, _I, _I, _I, _I, _vp]),
     "mhada_gemm_tn_splits": (_I, [_I, _I, _I]),
     "mhada_loss_attn": (_I, [_vp] * 7 + [_I, _I, _I, _I, _I, _I, _vp]),
     "mhada_rows_normalize": (_I, [_vp] * 4 + [_I, _I, _I, _I, _vp]),

@@ -533,9 +533,11 @@ def adaattn_forward(blk, fc: _Feat, fs: _Feat, fcs: _Feat, dt: torch.dtype, want
     return f
 
 
-def adaformer1_forward(ada, fc: Sequence[torch.Tensor], fs: Sequence[torch.Tensor]) -> torch.Tensor:
+def adaformer1_forward(ada, fc: Sequence[torch.Tensor], fs: Sequence[torch.Tensor],
+                       emit_u8: Optional[str] = None) -> torch.Tensor:
     """AdaAttnTransformer.forward (adaDecoder.py:226-232): num_layers single-head AdaAttN blocks and the
-    Decoder; returns cs.  No per-style cache (multi-head only)."""
+    Decoder; returns cs.  No per-style cache (multi-head only).  ``emit_u8``: as in
+    decoder_forward_tokens (cs is then the u8 frame)."""
     require_device(fc[0], "AdaAttnTransformer")
     dt = resolve_compute_dtype(ada)
     L = ada.num_layers
@@ -547,7 +549,7 @@ def adaformer1_forward(ada, fc: Sequence[torch.Tensor], fs: Sequence[torch.Tenso
                               want_bf16=(dt == torch.bfloat16 and i == L - 1))
     B, N, C = fcs.t.shape
     x16 = None if fcs.t16 is None else fcs.t16.view(B, fcs.h, fcs.w, C)
-    return decoder_forward_tokens(ada.decoder, fcs.t.view(B, fcs.h, fcs.w, C), dt, x16=x16)
+    return decoder_forward_tokens(ada.decoder, fcs.t.view(B, fcs.h, fcs.w, C), dt, x16=x16, emit_u8=emit_u8)
 
 
 def style_cache(ada, fs: Sequence[torch.Tensor], dt: torch.dtype):
@@ -594,10 +596,13 @@ def decoder_prep(dec, dtype):
 
 
 def decoder_forward_tokens(dec, x_nhwc: torch.Tensor, dt: torch.dtype, clamp255: bool = False,
-                           x16: Optional[torch.Tensor] = None) -> torch.Tensor:
+                           x16: Optional[torch.Tensor] = None, emit_u8: Optional[str] = None) -> torch.Tensor:
     """Decoder.forward (conv.py:96-100) on NHWC input; returns NCHW fp32 (B,3,8h,8w).  ``x16``: a
     bf16 copy of the input (bf16 compute: the first conv then runs on the bf16 ping-pong GEMM
-    instead of converting fp32 rows on load)."""
+    instead of converting fp32 rows on load).  ``emit_u8`` = "bgr" | "rgb": the last layer writes
+    the clamped u8 frame (B,8h,8w,3) in that channel order instead (ops.conv3x3_out3_u8)."""
+    if emit_u8 not in (None, "bgr", "rgb"):
+        raise ValueError(f'emit_u8 must be None, "bgr" or "rgb", got {emit_u8!r}')
     prep = decoder_prep(dec, dt)
     x = x16 if (x16 is not None and dt == torch.bfloat16) else x_nhwc
     for w, b, up, u in prep["layers"]:
@@ -605,11 +610,14 @@ def decoder_forward_tokens(dec, x_nhwc: torch.Tensor, dt: torch.dtype, clamp255:
             x = ops.upsample2x(x)
             up = False
         x = ops.conv3x3(x, w, b, dt, upsample=up, relu=True, wino_u=u)
+    if emit_u8 is not None:
+        return ops.conv3x3_out3_u8(x, prep["w_last"], prep["b_last"], bgr=(emit_u8 == "bgr"))
     return ops.conv3x3_out3(x, prep["w_last"], prep["b_last"], clamp255=clamp255)
 
 
-def adaformer_forward(ada, fc: Sequence[torch.Tensor], fs: Sequence[torch.Tensor]):
-    """AdaAttnTransformerMultiHead.forward (adaDecoder.py:253-268): returns (fcs, cs)."""
+def adaformer_forward(ada, fc: Sequence[torch.Tensor], fs: Sequence[torch.Tensor], emit_u8: Optional[str] = None):
+    """AdaAttnTransformerMultiHead.forward (adaDecoder.py:253-268): returns (fcs, cs).  ``emit_u8``: as in
+    decoder_forward_tokens (cs is then the u8 frame)."""
     require_device(fc[0], "AdaAttnTransformerMultiHead")
     dt = resolve_compute_dtype(ada)
     L = ada.num_layers
@@ -623,5 +631,5 @@ def adaformer_forward(ada, fc: Sequence[torch.Tensor], fs: Sequence[torch.Tensor
                             want_bf16=(dt == torch.bfloat16 and i == L - 1))
     B, N, C = fcs.t.shape
     x16 = None if fcs.t16 is None else fcs.t16.view(B, fcs.h, fcs.w, C)
-    cs = decoder_forward_tokens(ada.decoder, fcs.t.view(B, fcs.h, fcs.w, C), dt, x16=x16)
+    cs = decoder_forward_tokens(ada.decoder, fcs.t.view(B, fcs.h, fcs.w, C), dt, x16=x16, emit_u8=emit_u8)
     return tokens_to_nchw(fcs.t, fcs.h, fcs.w), cs

@@ -355,6 +355,19 @@ def conv3x3_out3(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, clamp255:
     return y
 
 
+def conv3x3_out3_u8(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, bgr: bool = True,
+                    out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``mhada_conv3x3_out3_u8``: the last decoder layer writing the cv2-ready u8 frame [B][H][W][3]
+    (B,G,R for ``bgr``, else R,G,B) — bit for bit ``frame_emit(conv3x3_out3(x, w, bias, clamp255=True))``
+    with no fp32 frame in between.  ``out``: as in frame_emit."""
+    B, H, W, Ci = x.shape
+    _need_gpu(x, w, bias, out)
+    out = _u8_frames(out, B, H, W, x.device)
+    _call("mhada_conv3x3_out3_u8", x, x.data_ptr(), dt_code(x.dtype), w.data_ptr(), bias.data_ptr(),
+          out.data_ptr(), out.stride(1), int(bgr), B, H, W, Ci)
+    return out
+
+
 def layernorm(x: torch.Tensor, g: torch.Tensor, b: torch.Tensor, out_dtype: torch.dtype, eps: float) -> torch.Tensor:
     _need_gpu(x, g, b)
     rows, cols = x.shape
@@ -1511,6 +1524,37 @@ def frame_ingest(frames: torch.Tensor, out_hw=None, bgr: bool = True) -> torch.T
     Ho, Wo = (H, W) if out_hw is None else out_hw
     out = torch.empty(B, 3, Ho, Wo, device=frames.device, dtype=torch.float32)
     _call("mhada_frame_ingest", frames, frames.data_ptr(), B, H, W, frames.stride(1), int(bgr), out.data_ptr(), Ho, Wo)
+    return out
+
+
+def _u8_frames(out: Optional[torch.Tensor], B: int, H: int, W: int, device) -> torch.Tensor:
+    """The u8 [B][H][W][3] output of frame_emit / conv3x3_out3_u8: a new packed tensor, or the caller's
+    ``out`` checked under the stride rules frame_ingest accepts on input (packed pixels, rows of any
+    stride >= 3W, images H rows apart)."""
+    if out is None:
+        return torch.empty(B, H, W, 3, device=device, dtype=torch.uint8)
+    if out.dtype != torch.uint8 or out.device != device:
+        raise ValueError("out must be a uint8 tensor on the input's device")
+    if tuple(out.shape) != (B, H, W, 3) or out.stride(3) != 1 or out.stride(2) != 3:
+        raise ValueError(f"out must be [{B}][{H}][{W}][3] with packed pixels, got {tuple(out.shape)} "
+                         f"strides {tuple(out.stride())}")
+    if out.stride(1) < 3 * W or (B > 1 and out.stride(0) != H * out.stride(1)):
+        raise ValueError("out rows must be >= 3*W bytes apart and its images H rows apart")
+    return out
+
+
+def frame_emit(x: torch.Tensor, bgr: bool = True, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``mhada_frame_emit``, the inverse of frame_ingest: fp32 [B][3][H][W] (any range, R,G,B planes) ->
+    u8 frames [B][H][W][3], clamp(0, 255) then truncation (numpy ``astype(uint8)``; NaN -> 0), B,G,R
+    for ``bgr`` else R,G,B.  ``out``: a u8 [B][H][W][3] tensor to write in place; its rows may be
+    padded (a view of a wider buffer), and the padding bytes are not touched."""
+    _need_gpu(x, out)
+    if x.dtype != torch.float32 or x.dim() != 4 or x.shape[1] != 3:
+        raise ValueError(f"frame_emit expects a float32 [B][3][H][W] tensor, got {x.dtype} {tuple(x.shape)}")
+    x = x.contiguous()
+    B, _, H, W = x.shape
+    out = _u8_frames(out, B, H, W, x.device)
+    _call("mhada_frame_emit", x, x.data_ptr(), B, H, W, out.data_ptr(), out.stride(1), int(bgr))
     return out
 
 

@@ -4,10 +4,14 @@
 * ``flow_warp_mask(flo01, flo10, padding_mode, threshold)`` — utilities.py:121-151;
 * ``cv2_to_tensor(img, resize)`` — utilities.py:43-52 (BGR->RGB, INTER_AREA, toTensor255) as one
   HIP pass over the u8 frame in device memory (csrc/ingest.hip);
+* ``tensor_to_cv2(cs, bgr)`` — its counterpart, the output conversion of infer_video.py:94,110-112
+  (clamp(0,255) -> HWC -> uint8 -> RGB2BGR) as one HIP pass (mhada_frame_emit, csrc/ingest.hip);
 * ``warping_error(cs1, cs2, flow, mask)`` — the per-frame optical-flow metric of
   exps_sintel.py:101-109 (sum(mask * |cs2 - warp(cs1, flow)|) / (C*H*W));
 * ``VideoStylizer`` — the infer_video.py:58-92 loop: the style is encoded once and, through the
-  AdaFormer's per-style cache (engine.style_cache), its K/V projections are reused per frame.
+  AdaFormer's per-style cache (engine.style_cache), its K/V projections are reused per frame;
+  ``stylize_u8`` returns the cv2-ready u8 frame (mhada_frame_emit, or the decoder's last layer
+  writing it itself: mhada_conv3x3_out3_u8).
 
 The inference forms run the HIP kernels (csrc/warp.hip); the gradient through the warp w.r.t. the
 image (train_video.py temporal losses) runs its HIP adjoint (WarpFn / mhada_warp_bwd).
@@ -16,9 +20,10 @@ from __future__ import annotations
 
 from typing import Optional
 
+import numpy as np
 import torch
 
-from . import losses, ops
+from . import engine, losses, ops
 
 
 class WarpFn(torch.autograd.Function):
@@ -69,6 +74,49 @@ def cv2_to_tensor(img, resize: Optional[tuple] = None, device: Optional[torch.de
     return ops.frame_ingest(img, out_hw, bgr=True)[0]
 
 
+# VideoStylizer.stylize_u8's default route to the u8 frame.  False: the decoder ends in mhada_conv3x3_out3
+# and mhada_frame_emit converts its fp32 frame (two kernels); True: the fused mhada_conv3x3_out3_u8 (no fp32
+# frame in HBM).  Both give the same bits.  The fused kernel had to stay within the same-run A-against-A
+# spread of the mhada_conv3x3_out3 kernel time to become the default and did not in three of four cases
+# (tools/frame_emit_ab.py, profiles/r21_frame_emit_ab.log: +7.6 / +14.4 / +5.6 / -1.5 us against spreads
+# of 4.5 / 2.9 / 4.3 / 1.6 us; DESIGN.md §3a "Frame emit").
+STYLIZE_U8_FUSED = False
+
+
+def tensor_to_cv2(cs: torch.Tensor, bgr: bool = True):
+    """The output conversion of infer_video.py:94,110-112 (and exps_video.py / exps_sintel.py), the
+    counterpart of cv2_to_tensor: ``cs`` fp32 [3][H][W] or [B][3][H][W] in any range ->
+    ``cs.clamp(0, 255)``, channels last, ``astype(np.uint8)`` (truncation), and RGB->BGR when ``bgr``.
+
+    A device tensor takes the HIP pass (ops.frame_emit) and returns the uint8 device tensor
+    [H][W][3] / [B][H][W][3] (download it with ``.cpu().numpy()``, a quarter of the fp32 bytes).  A CPU
+    tensor evaluates the reference expression and returns the numpy array.  NaN gives 0 on the device
+    (numpy leaves it undefined)."""
+    if not isinstance(cs, torch.Tensor) or cs.dim() not in (3, 4):
+        raise ValueError("tensor_to_cv2 expects a [3][H][W] or [B][3][H][W] tensor")
+    if cs.shape[-3] != 3:
+        raise ValueError(f"tensor_to_cv2 expects 3 channels, got {cs.shape[-3]}")
+    if not cs.is_floating_point():
+        raise ValueError(f"tensor_to_cv2 expects a floating-point tensor, got {cs.dtype}")
+    single = cs.dim() == 3
+    x = cs.detach().unsqueeze(0) if single else cs.detach()
+    if x.is_cuda:
+        out = ops.frame_emit(x.float(), bgr=bgr)
+        return out[0] if single else out
+    out = x.float().clamp(0, 255).permute(0, 2, 3, 1).numpy().astype(np.uint8)
+    if bgr:
+        out = np.ascontiguousarray(out[..., ::-1])
+    return out[0] if single else out
+
+
+def _frames01(t: torch.Tensor) -> torch.Tensor:
+    """A warping_error operand as fp32 NCHW in [0, 1]: fp32 NCHW passes through; a uint8 frame
+    [B][H][W][3] (stylize_u8 / tensor_to_cv2) becomes its values / 255, channels first."""
+    if t.dtype == torch.uint8:
+        return (t.permute(0, 3, 1, 2).float() / 255.0).contiguous()
+    return t
+
+
 def flow_warp_mask(flo01: torch.Tensor, flo10: torch.Tensor, padding_mode: str = "zeros",
                    threshold: float = 2) -> torch.Tensor:
     """utilities.flow_warp_mask: forward/backward flow consistency mask [H,W] (1.0 = valid)."""
@@ -77,22 +125,30 @@ def flow_warp_mask(flo01: torch.Tensor, flo10: torch.Tensor, padding_mode: str =
 
 def warping_error(cs1: torch.Tensor, cs2: torch.Tensor, flow: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:
     """exps_sintel.py:101-109 per image: sum(mask * |cs2 - warp(cs1, flow)|) / (C*H*W).
-    mask is [B,H,W] (or [H,W] for B == 1)."""
+    mask is [B,H,W] (or [H,W] for B == 1).  cs1 / cs2: fp32 NCHW in [0, 1], or uint8 frames
+    [B][H][W][3] (both in one channel order), scored as their values / 255 — the quantised frames, as
+    exps_sintel.py scores them after its own round trip through uint8 images."""
     if mask.dim() == 2:
         mask = mask.unsqueeze(0)
-    return ops.warp_l1(cs1, cs2, flow, mask)
+    return ops.warp_l1(_frames01(cs1), _frames01(cs2), flow, mask)
 
 
 class VideoStylizer:
     """infer_video.py:58-92 on the drop-in modules: ``set_style(s)`` encodes the style once,
     ``__call__(frame)`` stylises one content frame [B,3,H,W] (0..255) against it and returns the
-    clamped output; ``warping_error(flow, mask)`` scores the last two outputs (exps_sintel)."""
+    clamped output; ``warping_error(flow, mask)`` scores the last two outputs (exps_sintel).
+    ``stylize_u8(frame)`` returns the frame as cv2 wants it (uint8, HWC, BGR), converted on the
+    device; it keeps the last two uint8 frames, so after it ``warping_error`` scores
+    the quantised frames (values / 255), as exps_sintel.py does after writing and re-reading images."""
 
     def __init__(self, vit_c, vit_s, ada):
         self.vit_c, self.vit_s, self.ada = vit_c, vit_s, ada
         self.fs = None
         self.prev: Optional[torch.Tensor] = None
         self.cur: Optional[torch.Tensor] = None
+        self._host = [None, None]  # stylize_u8(to_host=True): two pinned buffers, used alternately
+        self._host_ev = [None, None]
+        self._host_i = 0
 
     @torch.no_grad()
     def set_style(self, s: torch.Tensor) -> None:
@@ -108,7 +164,57 @@ class VideoStylizer:
         return cs
 
     @torch.no_grad()
+    def stylize_u8(self, frame: torch.Tensor, bgr: bool = True, to_host: bool = False,
+                   fused: Optional[bool] = None):
+        """Stylise one content frame [B,3,H,W] (0..255) and return it as uint8 [B][H][W][3], B,G,R
+        (``bgr``) or R,G,B: bit for bit the reference's clamp(0,255) -> HWC -> astype(uint8) (->
+        RGB2BGR) of what ``__call__`` returns.  ``fused`` (default STYLIZE_U8_FUSED): True — written by the
+        decoder's last kernel itself (mhada_conv3x3_out3_u8; the fp32 frame is never stored); False — the
+        decoder's fp32 frame converted by mhada_frame_emit.  The same bits either way.  Takes the
+        multi-head model or the single-head AdaAttnTransformer.
+
+        Returns the device tensor, or with ``to_host`` a numpy array (B, H, W, 3) — (H, W, 3) for a
+        [3,H,W] frame.  The download goes through two pinned host buffers used alternately: a
+        non-blocking copy on the current stream, then a wait on that copy's event only (not a device
+        synchronize).  The returned array is a COPY of the pinned buffer: it owns its memory, and later
+        calls never change it."""
+        if self.fs is None:
+            raise RuntimeError("VideoStylizer: call set_style(style_image) first")
+        single = frame.dim() == 3
+        if single:
+            frame = frame.unsqueeze(0)
+        fused = STYLIZE_U8_FUSED if fused is None else fused
+        emit = ("bgr" if bgr else "rgb") if fused else None
+        fc = self.vit_c(frame)
+        if hasattr(self.ada, "adaAttnHead"):
+            _, u8 = engine.adaformer_forward(self.ada, list(fc), list(self.fs), emit_u8=emit)
+        else:
+            u8 = engine.adaformer1_forward(self.ada, list(fc), list(self.fs), emit_u8=emit)
+        if not fused:
+            u8 = ops.frame_emit(u8, bgr=bgr)  # clamps: the bits of mhada_conv3x3_out3(clamp255 = 1) cast
+        self.prev, self.cur = self.cur, u8
+        if not to_host:
+            return u8[0] if single else u8
+        i = self._host_i
+        self._host_i ^= 1
+        if self._host[i] is None or self._host[i].shape != u8.shape:
+            self._host[i] = torch.empty(u8.shape, dtype=torch.uint8, pin_memory=True)
+            self._host_ev[i] = torch.cuda.Event()
+        self._host[i].copy_(u8, non_blocking=True)
+        self._host_ev[i].record()
+        self._host_ev[i].synchronize()
+        out = self._host[i].numpy().copy()
+        return out[0] if single else out
+
+    @torch.no_grad()
     def warping_error(self, flow: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:
+        """Scores the last two outputs: fp32 frames of ``__call__`` as values / 255, uint8 frames of
+        ``stylize_u8`` as their quantised values / 255 (the L1 sum is the same for B,G,R and R,G,B)."""
         if self.prev is None:
             raise RuntimeError("VideoStylizer: need two frames")
+        if self.prev.dtype != self.cur.dtype:
+            raise RuntimeError("VideoStylizer: the last two frames come from different calls (__call__ and "
+                               "stylize_u8); score two frames of one kind")
+        if self.cur.dtype == torch.uint8:
+            return warping_error(self.prev, self.cur, flow, mask)
         return warping_error(self.prev / 255.0, self.cur / 255.0, flow, mask)
