@@ -32,38 +32,13 @@ __global__ void __launch_bounds__(256) layernorm_kernel(const float* __restrict_
     const f32x4 t = *reinterpret_cast<const f32x4*>(xr + (i * 64 + lane) * 4);
     v[4 * i] = t[0]; v[4 * i + 1] = t[1]; v[4 * i + 2] = t[2]; v[4 * i + 3] = t[3];
   }
-  if constexpr (FORM == 2) {
-    // The fp32 LayerNorm with its roundings pinned (no implicit contraction, the two fused steps
-    // written out), so the planes are those of the fp32 form's output bit for bit: the fp32
-    // instantiation at cols = 512 rounds mean, v - mean and its square, fuses sum / COLS + eps and
-    // t * gamma + beta.  Then the two fp16 planes of scale * y.
+  // One arithmetic for every output form, its roundings pinned (no implicit contraction, the two fused steps
+  // written out): mean, v - mean and its square round, sum / COLS + eps and t * gamma + beta are fused.  The
+  // plane forms are therefore the documented splits of the fp32 form's output bit for bit, at every width
+  // (left to the compiler, the instantiations contracted differently and the BF16X3 planes at cols = 512
+  // differed from the split of the fp32 output in the last bit).
+  {
 #pragma clang fp contract(off)
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < VPL; ++i) s += v[i];
-    const float mean = wave_sum(s) * (1.0f / COLS);
-    float ss = 0.f;
-#pragma unroll
-    for (int i = 0; i < VPL; ++i) {
-      v[i] = v[i] - mean;
-      ss += v[i] * v[i];
-    }
-    const float rstd = rsqrtf(fmaf(wave_sum(ss), 1.0f / COLS, eps));
-    TO* yr = y + (long long)row * COLS;
-    const long long plane = (long long)rows * COLS;
-#pragma unroll
-    for (int i = 0; i < VPL / 4; ++i) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int c = (i * 64 + lane) * 4 + e;
-        const float sv = fmaf(v[4 * i + e] * rstd, g[c], b[c]) * scale;
-        const f16 hi = half2_plane(sv);
-        yr[c] = hi;
-        yr[plane + c] = half2_plane(sv - (float)hi);
-      }
-    }
-    return;
-  }
   float s = 0.f;
 #pragma unroll
   for (int i = 0; i < VPL; ++i) s += v[i];
@@ -71,10 +46,10 @@ __global__ void __launch_bounds__(256) layernorm_kernel(const float* __restrict_
   float ss = 0.f;
 #pragma unroll
   for (int i = 0; i < VPL; ++i) {
-    const float d = v[i] - mean;
-    ss += d * d;
+    v[i] = v[i] - mean;
+    ss += v[i] * v[i];
   }
-  const float rstd = rsqrtf(wave_sum(ss) * (1.0f / COLS) + eps);
+  const float rstd = rsqrtf(fmaf(wave_sum(ss), 1.0f / COLS, eps));
   TO* yr = y + (long long)row * COLS;
   const long long plane = (long long)rows * COLS;
 #pragma unroll
@@ -82,8 +57,13 @@ __global__ void __launch_bounds__(256) layernorm_kernel(const float* __restrict_
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const int c = (i * 64 + lane) * 4 + e;
-      const float val = (v[4 * i + e] - mean) * rstd * g[c] + b[c];
-      if constexpr (FORM == 1) {  // three bf16 planes: val = p0 + p1 + p2 to 2^-25 (the SPLIT3 GEMM operand)
+      const float val = fmaf(v[4 * i + e] * rstd, g[c], b[c]);
+      if constexpr (FORM == 2) {  // the two fp16 planes of scale * y
+        const float sv = val * scale;
+        const f16 hi = half2_plane(sv);
+        yr[c] = hi;
+        yr[plane + c] = half2_plane(sv - (float)hi);
+      } else if constexpr (FORM == 1) {  // three bf16 planes: val = p0 + p1 + p2 to 2^-25 (the SPLIT3 GEMM operand)
         const bf16 p0 = (bf16)val;
         const float r1 = val - (float)p0;
         const bf16 p1 = (bf16)r1;
@@ -94,6 +74,7 @@ __global__ void __launch_bounds__(256) layernorm_kernel(const float* __restrict_
         yr[c] = from_f32<TO>(val);
       }
     }
+  }
   }
 }
 

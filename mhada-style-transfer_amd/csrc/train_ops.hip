@@ -758,21 +758,30 @@ __global__ void __launch_bounds__(256) attn_bwd_prep_kernel(const float* __restr
 // ======================================================================================
 // PosEmbedding resize adjoint: gpos[c][sy][sx] = sum over target pixels (oy, ox) of the bilinear
 // weight pos_embed_kernel gives source (sy, sx) times g[oy*ow + ox][c].  Gather per source pixel
-// over a window of target rows / columns that contains every one referencing it, re-deriving the
-// forward's indices and weights with its exact float operations (deterministic, no atomics).
+// over a window of target rows / columns that contains every one referencing it, deriving the
+// taps and weights of each target with pe_src below (deterministic, no atomics).
 // ======================================================================================
-MHADA_DEV void pe_src(int o, float sh, int n, int& i0, int& i1, float& l0, float& l1) {
-  const float sf = fmaxf(sh * ((float)o + 0.5f) - 0.5f, 0.f);
-  i0 = min((int)sf, n - 1);
+// Taps of target index o when n source pixels are resized to m.  The source coordinate (o + 0.5) n / m - 0.5
+// = ((2 o + 1) n - m) / (2 m), clamped at 0, is kept as an integer fraction: i0 is its exact floor and each weight
+// a single rounded quotient, so the adjoint is that of the exact resize matrix to one rounding per weight.  (The
+// forward rounds the coordinate in fp32 as aten's fp32 kernel does, which test_pos_embed pins; that leaves an
+// absolute error of a few ulps of the coordinate in each weight, which the adjoint need not repeat.)
+MHADA_DEV void pe_src(int o, int n, int m, int& i0, int& i1, float& l0, float& l1) {
+  const long long den = 2LL * m;
+  long long num = (2LL * o + 1) * n - m;
+  if (num < 0) num = 0;
+  const long long q = num / den;  // < n
+  const long long rem = num - q * den;
+  i0 = (int)q;
   i1 = i0 + (i0 < n - 1 ? 1 : 0);
-  l1 = sf - (float)i0;
-  l0 = 1.f - l1;
+  l1 = (float)rem / (float)den;
+  l0 = (float)(den - rem) / (float)den;
 }
 
-MHADA_DEV float pe_weight(int o, float sh, int n, int src) {
+MHADA_DEV float pe_weight(int o, int n, int m, int src) {
   int i0, i1;
   float l0, l1;
-  pe_src(o, sh, n, i0, i1, l0, l1);
+  pe_src(o, n, m, i0, i1, l0, l1);
   return (i0 == src ? l0 : 0.f) + (i1 == src ? l1 : 0.f);
 }
 
@@ -794,11 +803,11 @@ __global__ void __launch_bounds__(256) pos_embed_bwd_kernel(const float* __restr
     const int xlo = max(0, (int)floorf(((float)sx - 1.5f) / shx) - 1);
     const int xhi = min(ow - 1, (int)ceilf(((float)sx + 1.5f) / shx) + 1);
     for (int oy = ylo; oy <= yhi; ++oy) {
-      const float wy = pe_weight(oy, shy, bh, sy);
+      const float wy = pe_weight(oy, bh, oh, sy);
       if (wy == 0.f) continue;
       float row = 0.f;
       for (int ox = xlo; ox <= xhi; ++ox) {
-        const float wx = pe_weight(ox, shx, bw, sx);
+        const float wx = pe_weight(ox, bw, ow, sx);
         if (wx != 0.f) row += wx * g[((long long)oy * ow + ox) * C + c];
       }
       acc += wy * row;
