@@ -753,6 +753,30 @@ int mhada_out3_wgrad(const float* x, const float* dy, const float* y, float* dw,
 int mhada_patch_embed_dgrad(const float* dy, const float* w, float* dimg, int B, int C, int Ci, int H, int W,
                             mhada_stream_t stream);
 
+/* Image-quality metrics of eval.py on u8 frames in device memory (csrc/metrics.hip).  Added to ABI 18
+ * WITHOUT a version bump (purely additive, found by symbol; see the _hd entries).  Frames as in
+ * mhada_frame_ingest / mhada_frame_emit: [B][H][W][3] u8, rows of row_bytes >= 3W, images
+ * H * row_bytes apart; no byte at or past 3W of a row is read.
+ *
+ * mhada_ssim_u8: out[b] = SSIMMetric (eval.py:167-223, reduction "none") of frame b of `a` and of `b`:
+ * 11 x 11 window, zero padding 5, C1 = 0.01^2 and C2 = 0.03^2 on the [0, 255] values, mean over H x W
+ * and the 3 channels (the channel order does not matter).  window: HOST pointer to the 121 fp32
+ * weights [11][11] the reference builds (copied into the launch; widened exactly to fp64).  The five
+ * window moments, the map value and every reduction are fp64 in a fixed order, rounded to fp32 once:
+ * ssim(x, x) == 1 exactly, ssim(a, b) == ssim(b, a) and repeated calls bit for bit.  work:
+ * mhada_ssim_u8_work(B, H, W) doubles.  A null pointer, a size <= 0, row_bytes < 3W, more than
+ * 65535 tile rows (H / 32) or 21845 frames, or a short workspace return MHADA_ERR_ARG before any launch.
+ *
+ * mhada_hist_u8: hist [B][4][256] uint32 (zeroed by the call, then filled): planes 0..2 the counts of
+ * the three stored channels, plane 3 of the gray image (R*9798 + G*19235 + B*3735 + 2^14) >> 15
+ * (OpenCV 4's u8 BGR2GRAY), R = stored byte 2 when bgr != 0 and byte 0 otherwise.  Exact integer
+ * counts (H * W < 2^32). */
+long long mhada_ssim_u8_work(int B, int H, int W);
+int mhada_ssim_u8(const void* a, long long row_bytes_a, const void* b, long long row_bytes_b, int B, int H, int W,
+                  const float* window, double* work, long long work_doubles, float* out, mhada_stream_t stream);
+int mhada_hist_u8(const void* frames, int B, int H, int W, long long row_bytes, int bgr, unsigned int* hist,
+                  mhada_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -147,6 +147,9 @@ SIGNATURES = {
     "mhada_out3_dgrad": (_I, [_vp] * 5 + [_I] * 3 + [_vp]),
     "mhada_out3_wgrad_work": (_c_ll, [_I, _I, _I]),
     "mhada_out3_wgrad": (_I, [_vp] * 6 + [_c_ll, _I, _I, _I, _vp]),
+    "mhada_ssim_u8_work": (_c_ll, [_I, _I, _I]),
+    "mhada_ssim_u8": (_I, [_vp, _c_ll, _vp, _c_ll, _I, _I, _I, _vp, _vp, _c_ll, _vp, _vp]),
+    "mhada_hist_u8": (_I, [_vp, _I, _I, _I, _c_ll, _I, _vp, _vp]),
 }
 
 _lib = None

@@ -1558,6 +1558,84 @@ def frame_emit(x: torch.Tensor, bgr: bool = True, out: Optional[torch.Tensor] = 
     return out
 
 
+# ---- image-quality metrics on u8 frames (csrc/metrics.hip) -------------------------------
+def _u8_input(frames: torch.Tensor, what: str) -> torch.Tensor:
+    """u8 frames [B][H][W][3] (or one [H][W][3]) on the device, checked under frame_ingest's stride
+    rules (packed pixels, rows >= 3W bytes apart); images not H rows apart are copied."""
+    _need_gpu(frames)
+    if frames.dtype != torch.uint8:
+        raise ValueError(f"{what}: frames must be uint8, got {frames.dtype}")
+    if frames.dim() == 3:
+        frames = frames.unsqueeze(0)
+    if frames.dim() != 4 or frames.shape[3] != 3 or frames.stride(3) != 1 or frames.stride(2) != 3 or frames.numel() == 0:
+        raise ValueError(f"{what}: frames must be [B][H][W][3] with packed pixels, got {tuple(frames.shape)}")
+    B, H, W, _ = frames.shape
+    if frames.stride(1) < 3 * W:
+        raise ValueError(f"{what}: rows must be >= 3*W bytes apart (row_bytes {frames.stride(1)} < {3 * W})")
+    if B > 1 and frames.stride(0) != H * frames.stride(1):
+        frames = frames.contiguous()
+    return frames
+
+
+_SSIM_WINDOW = None
+
+
+def ssim_window() -> torch.Tensor:
+    """The [11][11] fp32 window of SSIMMetric (eval.py:180-184), built as the reference builds it:
+    linspace, exp, normalise and the outer product, each an fp32 torch operation on the CPU."""
+    global _SSIM_WINDOW
+    if _SSIM_WINDOW is None:
+        x = torch.linspace(-5, 5, 11)
+        g = torch.exp(-(x ** 2) / (2 * 1.5 ** 2))
+        g = g / g.sum()
+        _SSIM_WINDOW = (g[:, None] @ g[None, :]).contiguous()
+    return _SSIM_WINDOW
+
+
+def ssim_u8(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    """``mhada_ssim_u8``: per-image SSIM (eval.py:167-223, reduction "none") of two u8 frame batches
+    [B][H][W][3] (rows may be padded) -> fp32 [B]; fp64 inside, deterministic."""
+    a, b = _u8_input(a, "ssim_u8"), _u8_input(b, "ssim_u8")
+    _need_gpu(a, b)
+    if a.shape != b.shape:
+        raise ValueError(f"ssim_u8: shapes differ, {tuple(a.shape)} and {tuple(b.shape)}")
+    B, H, W, _ = a.shape
+    nwork = int(_lib.load().mhada_ssim_u8_work(B, H, W))
+    work = torch.empty(max(1, nwork), device=a.device, dtype=torch.float64)
+    out = torch.empty(B, device=a.device, dtype=torch.float32)
+    _call("mhada_ssim_u8", a, a.data_ptr(), a.stride(1), b.data_ptr(), b.stride(1), B, H, W, ssim_window().data_ptr(),
+          work.data_ptr(), nwork, out.data_ptr())
+    return out
+
+
+def hist_u8(frames: torch.Tensor, bgr: bool = True) -> torch.Tensor:
+    """``mhada_hist_u8``: exact counts int32 [B][4][256] of u8 frames [B][H][W][3] (rows may be
+    padded): the three stored channels, then the gray image of cv2's BGR2GRAY (RGB2GRAY without
+    ``bgr``).  (The library counts in uint32; below 2^31 pixels the int32 view holds the same values.)"""
+    frames = _u8_input(frames, "hist_u8")
+    B, H, W, _ = frames.shape
+    if H * W >= 1 << 31:
+        raise ValueError("hist_u8: 2^31 pixels or more per frame")
+    out = torch.empty(B, 4, 256, device=frames.device, dtype=torch.int32)
+    _call("mhada_hist_u8", frames, frames.data_ptr(), B, H, W, frames.stride(1), int(bgr), out.data_ptr())
+    return out
+
+
+def gram(feat: torch.Tensor) -> torch.Tensor:
+    """gram_matrix (eval.py:70-75) of fp32 features held NHWC, [B][H][W][C] or [B][P][C]: per image
+    X^T X / P with X = [P][C], on ``mhada_gemm_tn`` (A = B = X: fp32, deterministic split-K) -> [B][C][C]."""
+    _need_gpu(feat)
+    if feat.dtype != torch.float32 or feat.dim() not in (3, 4) or not feat.is_contiguous() or feat.numel() == 0:
+        raise ValueError("gram: contiguous fp32 NHWC features [B][H][W][C] (or [B][P][C])")
+    B, C = feat.shape[0], feat.shape[-1]
+    P = feat.numel() // (B * C)
+    if C % 4:
+        raise ValueError("gram: C must be a multiple of 4")
+    x = feat.view(B, P, C)
+    out = torch.stack([gemm_tn(x[i], x[i], M=C, N=C, K=P, lda=C, ldb=C) for i in range(B)])
+    return out.div_(P)
+
+
 # ---- training path (fp32, NHWC): backward helpers (include/mhada_hip.h) ------------------
 def gemm_tn(a: torch.Tensor, b: torch.Tensor, M: int, N: int, K: int, lda: int, ldb: int = 0,
             b_mode: int = A_ROWS, img=(0, 0, 0), pad: int = 0, colsum: bool = False, nb: int = 1,
