@@ -777,6 +777,21 @@ int mhada_ssim_u8(const void* a, long long row_bytes_a, const void* b, long long
 int mhada_hist_u8(const void* frames, int B, int H, int W, long long row_bytes, int bgr, unsigned int* hist,
                   mhada_stream_t stream);
 
+/* The distance head of LPIPS (lpips/__init__.py:13-15, lpips/lpips.py:139-147; csrc/lpips.hip).  Added
+ * to ABI 18 WITHOUT a version bump (purely additive, found by symbol).  fa, fb: fp32 [B][P][C], the
+ * NHWC storage of two feature maps with P = H * W pixels; w: fp32 [C], the layer's linear weights;
+ * out: fp64 [B],
+ *   out[b] = (1 / P) sum_p sum_c w_c (a_c / (|a| + 1e-10) - b_c / (|b| + 1e-10))^2,  |a| = sqrt(sum_c a_c^2).
+ * The per-pixel arithmetic is fp32 with the difference formed directly, the sum over the pixels fp64
+ * in a fixed order (per-workgroup partials in `work`, then a finalising launch; no atomics): fa == fb
+ * bit for bit gives exactly 0, an all-zero pixel vector contributes 0, (fa, fb) -> (fb, fa) and
+ * repeated calls return the same bits.  work: mhada_lpips_layer_work(B, P, C) doubles.  A null
+ * pointer, B <= 0, P <= 0 or >= 2^31, B > 65535, C not a multiple of 64 or above 512, a pointer not
+ * 16-byte aligned or a short workspace return MHADA_ERR_ARG before any launch. */
+long long mhada_lpips_layer_work(int B, long long P, int C);
+int mhada_lpips_layer(const float* fa, const float* fb, const float* w, int B, long long P, int C, double* work,
+                      long long work_doubles, double* out, mhada_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -150,6 +150,8 @@ SIGNATURES = {
     "mhada_ssim_u8_work": (_c_ll, [_I, _I, _I]),
     "mhada_ssim_u8": (_I, [_vp, _c_ll, _vp, _c_ll, _I, _I, _I, _vp, _vp, _c_ll, _vp, _vp]),
     "mhada_hist_u8": (_I, [_vp, _I, _I, _I, _c_ll, _I, _vp, _vp]),
+    "mhada_lpips_layer_work": (_c_ll, [_I, _c_ll, _I]),
+    "mhada_lpips_layer": (_I, [_vp, _vp, _vp, _I, _c_ll, _I, _vp, _c_ll, _vp, _vp]),
 }
 
 _lib = None

@@ -450,6 +450,30 @@ def vgg19_forward(vgg, x: torch.Tensor, masked_features: bool = False) -> Dict[s
     return feats
 
 
+VGG16_TAPS = ("relu1_2", "relu2_2", "relu3_3", "relu4_3", "relu5_3")
+
+
+def vgg16_forward(vgg, x: torch.Tensor) -> Dict[str, torch.Tensor]:
+    """The LPIPS trunk (lpips/pretrained_networks.py:122-136) on an image in [0, 255]: relu1_2, relu2_2,
+    relu3_3, relu4_3, relu5_3.  The ImageNet normalisation is LPIPS's ScalingLayer after im2tensor,
+    (u / 127.5 - 1 - shift) / scale = (u / 255 - (1 + shift) / 2) / (scale / 2).  On a ROCm device: the
+    kernels of train_fns.vgg19_forward over VGG16's slice table, inference only (in a VGG16 slice the pool
+    opens the next slice, so no conv's ReLU output feeds a pool of its own slice and every slice end is a
+    tap); on the CPU: aten."""
+    if x.is_cuda:
+        if torch.is_grad_enabled() and x.requires_grad:
+            raise NotImplementedError("network.VGG16 on the device is inference only (no gradient to the image)")
+        from network.vgg16 import _CONVS, _POOLS, _SLICES
+        from . import train_fns
+        return train_fns.vgg19_forward(vgg, x, {i for i, _, _ in _CONVS}, set(_POOLS), _SLICES, names=VGG16_TAPS)
+    x = imagenet_normalize(x)
+    feats = {}
+    for i, name in enumerate(VGG16_TAPS, start=1):
+        x = getattr(vgg, f"slice{i}")(x)
+        feats[name] = x
+    return feats
+
+
 def _tokens(x: torch.Tensor) -> torch.Tensor:
     """NCHW (any strides; free for channels-last views) -> contiguous fp32 [B][H*W][C]."""
     B, C, h, w = x.shape

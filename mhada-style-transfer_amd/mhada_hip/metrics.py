@@ -1,15 +1,18 @@
-"""Score stylised frames on the device: the eight weight-free numbers of the reference's result
-tables (eval.py, driven by exps_image.py), on u8 frames [B][H][W][3] in device memory — what
+"""Score stylised frames on the device: ten of the twelve numbers of the reference's result tables
+(eval.py, driven by exps_image.py; eight need no weights), on u8 frames [B][H][W][3] in device memory — what
 ``VideoStylizer.stylize_u8`` returns and what eval.py reads back from the PNG it wrote.
 
   ssim(a, b)                       SSIMMetric (eval.py:167-223)      mhada_ssim_u8, fp64 inside
   kl(a, b)                         kl_loss (eval.py:49-67)           mhada_hist_u8 + host fp64
   moment / uniformity / entropy    eval.py:111-164 on the gray image mhada_hist_u8 + host fp64
   gram(a, b, vgg)                  gram_loss (eval.py:78-108)        HIP VGG19, mhada_gemm_tn, mhada_feat_stats
+  lpips(a, b, vgg16, lins)         lpips.LPIPS(net="vgg") (eval.py:22)  HIP VGG16, mhada_lpips_layer
   score(stylized, content, style)  the CSV row of exps_image.py:90-123, one value per image
 
-LPIPS and SIFID need downloaded VGG16 / Inception weights and are not here (their keys are absent
-from ``score``, not NaN).  Frames may have padded rows; CPU tensors raise (no host fallback).  The
+LPIPS is here for callers who hand in a ``network.VGG16`` with ImageNet weights and the five linear
+vectors of an lpips checkout (``lpips_weights``): the package ships and fetches no weights, so there
+is no default, and without ``lpips=`` the two LPIPS keys are absent from ``score``, not NaN.  SIFID
+needs Inception and is not here.  Frames may have padded rows; CPU tensors raise (no host fallback).  The
 histogram metrics are finalised on the host from the 4 KB of exact counts, in numpy fp64 as the
 reference computes them; the ``*_from_counts`` functions are that arithmetic and need no GPU.
 
@@ -19,7 +22,7 @@ C2 = 0.03^2 applied to [0, 255] values the fp32 evaluation is rounding noise on 
 """
 from __future__ import annotations
 
-from typing import Dict, Optional
+from typing import Dict, List, Optional
 
 import numpy as np
 import torch
@@ -27,7 +30,10 @@ import torch
 from . import ops
 
 SCORE_KEYS = ("ssim_content", "kl_c", "ssim_style", "kl_s", "gram", "moment", "uniformity", "entropy")
+SCORE_KEYS_LPIPS = ("lpips_content", "ssim_content", "kl_c", "lpips_style", "ssim_style", "kl_s", "gram", "moment",
+                    "uniformity", "entropy")  # the reference's CSV order, without sifid
 _VGG_LAYERS = tuple(f"relu{i}_1" for i in range(1, 6))
+_LPIPS_CHNS = (64, 128, 256, 512, 512)  # lpips.py:91
 
 
 # ---- host finalisers: counts -> numbers (numpy fp64; no GPU, no scipy) ---------------------
@@ -144,12 +150,82 @@ def gram(a_u8: torch.Tensor, b_u8: torch.Tensor, vgg=None, bgr: bool = True) -> 
     return gram_from_features(vgg_features(a_u8, vgg, bgr), vgg_features(b_u8, vgg, bgr))
 
 
+def lpips_weights(src) -> List[torch.Tensor]:
+    """The five linear-layer vectors of LPIPS(net="vgg", version="0.1") as fp32 CPU tensors [C], C = 64, 128,
+    256, 512, 512, from a LOCAL ``weights/v0.1/vgg.pth`` of an lpips checkout, a path to it or its
+    state_dict: exactly the keys ``lin{0..4}.model.1.weight`` of shape (1, C, 1, 1) (strict).  Loaded with
+    ``weights_only=True`` onto the CPU (the shipped file was saved from a CUDA device)."""
+    sd = torch.load(src, map_location="cpu", weights_only=True) if not isinstance(src, dict) else src
+    want = {f"lin{k}.model.1.weight": (1, c, 1, 1) for k, c in enumerate(_LPIPS_CHNS)}
+    if set(sd) != set(want):
+        raise KeyError(f"lpips_weights: expected the keys {sorted(want)}, got {sorted(sd)}")
+    for key, shape in want.items():
+        if tuple(sd[key].shape) != shape:
+            raise ValueError(f"lpips_weights: {key} must be {shape}, got {tuple(sd[key].shape)}")
+    return [sd[key].detach().to("cpu", torch.float32).reshape(-1).contiguous() for key in want]
+
+
+@torch.no_grad()
+def vgg16_features(frames_u8: torch.Tensor, vgg16, bgr: bool = True):
+    """relu1_2, relu2_2, relu3_3, relu4_3, relu5_3 of u8 frames as contiguous NHWC fp32 tensors:
+    ops.frame_ingest (BGR->RGB, 0..255 fp32) then the HIP VGG16, whose fused normalisation is LPIPS's
+    im2tensor + ScalingLayer."""
+    feats = vgg16(ops.frame_ingest(frames_u8, bgr=bgr))
+    return [feats[k].permute(0, 2, 3, 1).contiguous() for k in ("relu1_2", "relu2_2", "relu3_3", "relu4_3", "relu5_3")]
+
+
+def _check_lins(lins) -> None:
+    if len(lins) != len(_LPIPS_CHNS):
+        raise ValueError(f"lpips: {len(_LPIPS_CHNS)} linear-layer vectors are needed (lpips_weights), got {len(lins)}")
+
+
+def _lins_on(lins, device) -> List[torch.Tensor]:
+    _check_lins(lins)
+    return [w.to(device=device, dtype=torch.float32).contiguous() for w in lins]
+
+
+@torch.no_grad()
+def lpips_from_features(feats_a, feats_b, lins, per_layer: bool = False) -> np.ndarray:
+    """LPIPS.forward (lpips.py:139-156) per image from two lists of the five NHWC feature maps: float64 [B],
+    the layers' distances (ops.lpips_layer) added in order 0..4; per_layer: the [5][B] distances themselves."""
+    if len(feats_a) != len(_LPIPS_CHNS) or len(feats_b) != len(_LPIPS_CHNS):
+        raise ValueError(f"lpips: {len(_LPIPS_CHNS)} feature maps per image are needed")
+    lins = _lins_on(lins, feats_a[0].device)
+    layers = torch.stack([ops.lpips_layer(fa, fb, w) for fa, fb, w in zip(feats_a, feats_b, lins)]).cpu().numpy()
+    if per_layer:
+        return layers
+    out = np.zeros(layers.shape[1])
+    for layer in layers:  # the reference adds the layers in order
+        out = out + layer
+    return out
+
+
+def lpips(a_u8: torch.Tensor, b_u8: torch.Tensor, vgg16=None, lins=None, bgr: bool = True,
+          per_layer: bool = False) -> np.ndarray:
+    """lpips.LPIPS(net="vgg")(im2tensor(a), im2tensor(b)) per image -> float64 [B] ([5][B] per layer).
+    ``vgg16``: a ``network.VGG16`` on the frames' device with ImageNet weights
+    (``VGG16.load_torchvision_features``); ``lins``: ``lpips_weights(...)``.  Neither has a default."""
+    if vgg16 is None or lins is None:
+        raise ValueError("lpips: pass vgg16=network.VGG16() with its weights loaded and lins=lpips_weights(path)")
+    _check_lins(lins)  # before any launch
+    return lpips_from_features(vgg16_features(a_u8, vgg16, bgr), vgg16_features(b_u8, vgg16, bgr), lins, per_layer)
+
+
 def score(stylized_u8: torch.Tensor, content_u8: torch.Tensor, style_u8: torch.Tensor, bgr: bool = True,
-          vgg=None) -> Dict[str, np.ndarray]:
-    """The weight-free columns of exps_image.py's CSV (SCORE_KEYS) for a batch: float64 [B] per key.
-    ``vgg`` as in ``gram``; without one the ``gram`` key cannot be computed and the call raises."""
+          vgg=None, lpips=None) -> Dict[str, np.ndarray]:
+    """The columns of exps_image.py's CSV for a batch, float64 [B] per key: the weight-free SCORE_KEYS, or
+    with ``lpips=(vgg16, lins)`` (as in ``lpips``) the ten SCORE_KEYS_LPIPS in the CSV's order; the stylised
+    frames' VGG16 features are computed once for both LPIPS columns.  ``vgg`` as in ``gram``; without one
+    the ``gram`` key cannot be computed and the call raises."""
     if vgg is None:
         raise ValueError("score: pass vgg=network.VGG19() with its weights loaded (needed for 'gram')")
+    lp = {}
+    if lpips is not None:
+        vgg16, lins = lpips
+        _check_lins(lins)  # before any launch
+        fs = vgg16_features(stylized_u8, vgg16, bgr)
+        lp = {"lpips_content": lpips_from_features(fs, vgg16_features(content_u8, vgg16, bgr), lins),
+              "lpips_style": lpips_from_features(fs, vgg16_features(style_u8, vgg16, bgr), lins)}
     hs = _hist(stylized_u8, bgr)
     out = {
         "ssim_content": ssim(stylized_u8, content_u8, "none").double().cpu().numpy(),
@@ -162,4 +238,7 @@ def score(stylized_u8: torch.Tensor, content_u8: torch.Tensor, style_u8: torch.T
         "entropy": entropy_from_counts(hs[:, 3]),
     }
     assert tuple(out) == SCORE_KEYS
+    if lp:
+        out.update(lp)
+        out = {k: out[k] for k in SCORE_KEYS_LPIPS}
     return out

@@ -1636,6 +1636,35 @@ def gram(feat: torch.Tensor) -> torch.Tensor:
     return out.div_(P)
 
 
+def lpips_layer(fa: torch.Tensor, fb: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
+    """``mhada_lpips_layer``: the LPIPS distance of one layer (lpips.py:139-147) of two fp32 feature maps
+    held NHWC, [B][H][W][C] or [B][P][C], with the linear weights w [C] -> float64 [B]: per pixel
+    unit-normalise both vectors over C (eps 1e-10 added to the norm), sum_c w_c (a^_c - b^_c)^2 in fp32,
+    then the fp64 mean over the pixels.  One pass over each map, deterministic.  C % 64 == 0, C <= 512."""
+    _need_gpu(fa, fb, w)
+    if any(t.dtype != torch.float32 for t in (fa, fb, w)):
+        raise ValueError(f"lpips_layer: fp32 features and weights, got {fa.dtype}, {fb.dtype}, {w.dtype}")
+    if fa.dim() not in (3, 4) or fa.shape != fb.shape or fa.numel() == 0:
+        raise ValueError(f"lpips_layer: two NHWC feature maps [B][H][W][C] (or [B][P][C]) of one shape, got "
+                         f"{tuple(fa.shape)} and {tuple(fb.shape)}")
+    if not (fa.is_contiguous() and fb.is_contiguous() and w.is_contiguous()):
+        raise ValueError("lpips_layer: contiguous NHWC storage (an NCHW view is not; permute(0, 2, 3, 1) first)")
+    B, C = fa.shape[0], fa.shape[-1]
+    if C % 64 or C > 512:
+        raise ValueError(f"lpips_layer: C must be a multiple of 64 and at most 512, got {C}")
+    if tuple(w.shape) != (C,):
+        raise ValueError(f"lpips_layer: w must be [{C}], got {tuple(w.shape)}")
+    if (fa.data_ptr() | fb.data_ptr() | w.data_ptr()) & 15:
+        raise ValueError("lpips_layer: the tensors must start on 16-byte boundaries")
+    P = fa.numel() // (B * C)
+    nwork = int(_lib.load().mhada_lpips_layer_work(B, P, C))
+    work = torch.empty(max(1, nwork), device=fa.device, dtype=torch.float64)
+    out = torch.empty(B, device=fa.device, dtype=torch.float64)
+    _call("mhada_lpips_layer", fa, fa.data_ptr(), fb.data_ptr(), w.data_ptr(), B, P, C, work.data_ptr(), nwork,
+          out.data_ptr())
+    return out
+
+
 # ---- training path (fp32, NHWC): backward helpers (include/mhada_hip.h) ------------------
 def gemm_tn(a: torch.Tensor, b: torch.Tensor, M: int, N: int, K: int, lda: int, ldb: int = 0,
             b_mode: int = A_ROWS, img=(0, 0, 0), pad: int = 0, colsum: bool = False, nb: int = 1,

@@ -750,12 +750,14 @@ def decoder_forward(dec, x_nchw: torch.Tensor, order) -> torch.Tensor:
     return x.permute(0, 3, 1, 2).contiguous()
 
 
-def vgg19_forward(vgg, img: torch.Tensor, convs, pools, slices, masked_features: bool = False) -> Dict[str, torch.Tensor]:
+def vgg19_forward(vgg, img: torch.Tensor, convs, pools, slices, masked_features: bool = False,
+                  names=None) -> Dict[str, torch.Tensor]:
     """VGG19.forward (vgg19.py:42-70) on the HIP kernels: relu1_1 .. relu5_1 as NCHW views of
     NHWC storage.  masked_features (the Trainer's fused losses only): the caller guarantees that every
     gradient reaching a feature map relu2_1 .. relu5_1 comes from a FeatureLossFn(relu_input=True),
     so the convs producing them skip their ReLU adjoint: the loss backward applies it, and the next
-    slice's first conv applies it in its dgrad (relu_input)."""
+    slice's first conv applies it in its dgrad (relu_input).  ``names``: the keys of the five slice
+    outputs when they are not relu{s}_1 (network.VGG16, whose slices end in relu1_2 .. relu5_3)."""
     x = None
     relu_to_pool = False
     relu_in = False
@@ -784,5 +786,5 @@ def vgg19_forward(vgg, img: torch.Tensor, convs, pools, slices, masked_features:
                 x = MaxPool2Fn.apply(x, relu_to_pool)
                 relu_to_pool = False
             # ReLU modules are fused into the conv epilogue
-        feats[f"relu{s}_1"] = nhwc_to_nchw(x)
+        feats[names[s - 1] if names else f"relu{s}_1"] = nhwc_to_nchw(x)
     return feats
