@@ -62,7 +62,7 @@ const char* mhada_last_error(void);
  * 8-wave grid has fewer blocks than CUs), attn_tk (64|128), attn_prio (0|1), vit_attn_vec (0|1),
  * out3_mfma (0|1), out3_tile (0|1), gemm_pp (0|1), gemm_persist (0|1), gemm_pp128 (0|1),
  * gemm_ldsepi (0|1), gemm_n64 (128|256), conv_c64 (0|1), conv_dir (0|1), gemm_rinit (0|1), tn_skinny_lds (0|1),
- * train_dkv_dma (0|1), wino4 (0|1), wino_split3 (0|1; ABI 17), gemm_s3_order (0|1; 1, the default: the SPLIT3 GEMM stages each operand plane once per K chunk, 0: the six-K-tile walk; same ABI), upsample_quad (0|1; ABI 16), xknob (0..15, read by no shipped dispatch).
+ * train_dkv_dma (0|1), wino4 (0|1), wino_split3 (0|1; ABI 17), gemm_s3_order (0|1; 1, the default: the SPLIT3 GEMM stages each operand plane once per K chunk, 0: the six-K-tile walk; same ABI), upsample_quad (0|1; ABI 16), wino_s3_rows (0|1; the SPLIT3 Winograd conv with one Winograd row per wave, bit-identical to 0, the kernel of ABI 17; same ABI), xknob (0..15, read by no shipped dispatch).
  * Returns MHADA_ERR_ARG for an unknown knob or an out-of-range value.  No reference
  * counterpart (the reference has no kernels). */
 int mhada_set_tuning(const char* name, int value);

@@ -42,7 +42,7 @@ const Knob kKnobs[] = {
     {"tn_skinny_lds", &Tuning::tn_skinny_lds},       {"train_dkv_dma", &Tuning::train_dkv_dma},
     {"wino_split3", &Tuning::wino_split3},           {"gemm_s3_order", &Tuning::gemm_s3_order},
     {"wino4", &Tuning::wino4},                       {"upsample_quad", &Tuning::upsample_quad},
-    {"xknob", &Tuning::xknob},
+    {"wino_s3_rows", &Tuning::wino_s3_rows},         {"xknob", &Tuning::xknob},
 };
 
 Tuning g_tuning;

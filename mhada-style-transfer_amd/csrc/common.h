@@ -46,6 +46,7 @@ struct Tuning {
   int tn_skinny_lds = 1;     // M <= 4 conv weight gradient: LDS-tiled kernel (0: the gather kernel)
   int wino4 = 1;             // fp32 Winograd conv: 4-wave kernel (round 5; 0: the 8-wave kernel, also the fallback for inputs >= 2 GiB)
   int wino_split3 = 1;       // fp32 Winograd conv, Cin % 16 == 0, with the filters' plane image: SPLIT3 products on the bf16 MFMA (0: wino4 / the 8-wave kernel)
+  int wino_s3_rows = 1;      // SPLIT3 Winograd conv: one Winograd row per wave, U from registers, wave-private V (0: wino_s3_kernel; bit-identical)
   int gemm_s3_order = 1;     // SPLIT3 GEMM: terms ordered so each operand plane is staged once per K chunk, separate A / W rings (0: six K-tiles per chunk, both operands staged for each)
   int train_dkv_dma = 1;     // training dK/dV' with the dS spill: LDS-DMA kernel, one wave per SIMD, software-pipelined (0: round 3's)
   int upsample_quad = 1;     // bf16 bilinear x2: 2 x 2-output-block kernel (0: the 16-B per-pixel kernel)

@@ -32,6 +32,8 @@
 // remains the fallback for inputs of 2 GiB and more (wino4 addresses x by a buffer resource).
 // Round 7: with the filters' plane image and Cin % 16 == 0 the default is wino_s3_kernel (SPLIT3
 // products on the bf16 MFMA, below); wino4_kernel and wino_kernel are unchanged.
+// Round 29: the SPLIT3 form runs one Winograd row per wave (wino_s3_rows_kernel, tuning wino_s3_rows; bit-identical to
+// wino_s3_kernel, which the knob's 0 keeps).
 // LDS operand rows are 32 B (8 channels) with the two 16-B halves swapped on rows with bit 3
 // set (swz), so the ds_read_b128 of 32 consecutive rows is conflict-free; the raw patch's 16-B
 // slots are XOR-swizzled (rswz) so the transform's ds_read_b32 hit distinct banks.
@@ -784,6 +786,263 @@ __global__ void __launch_bounds__(256, 1) wino_s3_kernel(const WinoS3P p) {
   }
 }
 
+// ------------------------------------------------------------------------------------
+// SPLIT3 form, one Winograd row per wave (tuning wino_s3_rows): the workgroup tile, grid order, raw
+// patch DMA, plane image and every MFMA (operand bits, accumulator, chunk and term order) of
+// wino_s3_kernel, so the result is bit-identical to it; the waves divide the 16 positions, not the
+// 64 x 64 block.  Wave w owns positions 4w .. 4w+3 of all 64 tiles x 64 channels (4 positions x 2 tile
+// blocks x 2 channel blocks of 32 x 32: 256 accumulator registers, as before), which removes LDS work:
+//   * a V fragment serves two channel blocks and a U fragment two tile blocks: per chunk and wave
+//     24 ds_read_b128 of V where wino_s3_kernel reads 96 of V and U;
+//   * no two waves share a position, so U never enters LDS: lane (r32, h) of channel block cb loads
+//     its 16 B of (position, plane) g from the image (L2) into registers, one position ahead of the
+//     MFMAs.  L2 traffic per workgroup is the 96 KiB per chunk of wino_s3_kernel's DMA.  (Feeding
+//     wino_s3_kernel's layout from registers doubled it: there two waves shared each U row.)
+//   * wave w transforms row w of V = B^T d B for all 64 tiles itself (4 items of (tile, 4 channels)
+//     per lane and chunk, wino_s3_kernel's lane -> (tile, quad) pattern and arithmetic; the row's
+//     sign enters as an exact +-1 factor) into a wave-private 24-KiB V region and reads its own
+//     fragments back: V needs no workgroup barrier.  Positions 0-1 of chunk k+1 are written beside
+//     the MFMAs of positions 0-1 of chunk k (whose fragments are in registers by then), positions
+//     2-3, held in registers meanwhile, beside those of positions 2-3.
+// One barrier per chunk remains: it publishes the raw patch of chunk k+2, DMA'd during chunk k.
+// LDS: 4 x 24 KiB of V (one object) + 2 x 21 KiB raw (two objects, selected at compile time).
+// The output transform crosses waves: wave i forms m[i][q] (the right multiplication by A) from its
+// own accumulators and hands it over through the V space, one q at a time (64 KiB); every wave then
+// finishes 16 tiles x 64 channels with wino4_kernel's expressions, lanes along the channels.
+// ------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256, 1) wino_s3_rows_kernel(const WinoS3P p) {
+  __shared__ __attribute__((aligned(16))) unsigned char sV[4 * kSStage];
+  __shared__ __attribute__((aligned(16))) unsigned char sR0[kSRawB];
+  __shared__ __attribute__((aligned(16))) unsigned char sR1[kSRawB];
+  const int tid = threadIdx.x, lane = tid & 63, h = lane >> 5, r32 = lane & 31;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+
+  // logical block: wino_s3_kernel's order
+  int id = xcd_remap(blockIdx.x, p.nblk);
+  const int nsp = p.nblk / p.nbn;
+  const int nb = id / nsp;
+  id -= nb * nsp;
+  const int bx = id % p.nbx;
+  id /= p.nbx;
+  const int by = id % p.nby;
+  const int b = id / p.nby;
+  const int co0 = nb * kCO;
+  const int P = p.zero ? p.pad : 1;
+  const int nck = p.Cin / kSK;
+
+  const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(
+      const_cast<float*>(p.x), 0, (int)((long long)p.B * p.H * p.W * p.Cin * 4), 0x00020000);
+  const __amdgpu_buffer_rsrc_t ur =
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16*>(p.up), 0, p.Cin * p.Cout * 96, 0x00020000);
+  // raw patch DMA: wino_s3_kernel's slots
+  int rvo[6];
+#pragma unroll
+  for (int t = 0; t < 6; ++t) {
+    const int slot = 64 * (wave + 4 * t) + lane;
+    const int pix = rpix(slot >> 2);
+    int iy = 2 * by * kT - P + pix / kRP, ix = 2 * bx * kT - P + pix % kRP;
+    bool inside = pix < kRaw;
+    if (p.zero) {
+      inside = inside && iy >= 0 && iy < p.H && ix >= 0 && ix < p.W;
+    } else {
+      iy = reflect_clamp(iy, p.H);
+      ix = reflect_clamp(ix, p.W);
+    }
+    rvo[t] = inside ? (((b * p.H + iy) * p.W + ix) * p.Cin + 4 * (slot & 3)) * 4 : 0x7ff00000;
+  }
+  typedef __attribute__((address_space(3))) void* LdsP;
+  auto dma_raw = [&](int k, unsigned char* sr) {
+    const int so = min(k, nck - 1) * kSK * 4;
+#pragma unroll
+    for (int t = 0; t < 6; ++t)
+      if (t < 5 || wave == 0)
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(xr, (LdsP)(sr + (wave + 4 * t) * 1024), 16, (unsigned)rvo[t], so, 0, 0);
+  };
+  // U fragments of position j of chunk k: [plane][channel block], straight from the image
+  const int uvo = ((co0 + r32) * kSK + 8 * h) * 2;
+  const int ugb = p.Cout * kSK * 2;  // bytes of one (position, plane) image
+  auto load_u = [&](int k, int j, bf16x8 (&u)[3][2]) {
+    const int so = (min(k, nck - 1) * 48 + (4 * wave + j) * 3) * ugb;
+#pragma unroll
+    for (int pl = 0; pl < 3; ++pl)
+#pragma unroll
+      for (int cb = 0; cb < 2; ++cb)
+        u[pl][cb] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(ur, uvo + cb * 1024, so + pl * ugb, 0));
+  };
+
+  // transform items it = 0..3: channels 4 tq .. 4 tq + 3 of tile 16 it + tl.  Row `wave` of B^T d is
+  // d[RA] + sg d[RB]: (0, 2, -), (1, 2, +), (2, 1, -), (1, 3, -).  rpix(pix + 72) = rpix(pix) + 72,
+  // so item it is item 0 plus 72 it pixels (4 patch rows) and 16 it tiles.
+  unsigned char* const sv = sV + wave * kSStage;
+  const int tq = lane & 3, tl = lane >> 2;
+  const int RA = wave == 0 ? 0 : (wave == 2 ? 2 : 1), RB = wave == 3 ? 3 : (wave == 2 ? 1 : 2);
+  const float sg = wave == 1 ? 1.f : -1.f;
+  int roffs[8];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    roffs[j] = rpix((2 * (tl >> 3) + RA) * kRP + 2 * (tl & 7) + j) * 64 + tq * 16;
+    roffs[4 + j] = rpix((2 * (tl >> 3) + RB) * kRP + 2 * (tl & 7) + j) * 64 + tq * 16;
+  }
+  const int vdst = tl * 32 + ((((tq >> 1) ^ (tl >> 3)) & 1) << 4) + (tq & 1) * 8;
+  auto split_store = [&](const f32x4 v, int x, int it) {  // the three planes of position x of item it
+    bf16x4 p0, p1, p2;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const bf16 a = (bf16)v[e];
+      const float r = v[e] - (float)a;
+      const bf16 c = (bf16)r;
+      p0[e] = a;
+      p1[e] = c;
+      p2[e] = (bf16)(r - (float)c);
+    }
+    *reinterpret_cast<bf16x4*>(sv + (3 * x + 0) * kSImg + it * 512 + vdst) = p0;
+    *reinterpret_cast<bf16x4*>(sv + (3 * x + 1) * kSImg + it * 512 + vdst) = p1;
+    *reinterpret_cast<bf16x4*>(sv + (3 * x + 2) * kSImg + it * 512 + vdst) = p2;
+  };
+  f32x4 hold[4][2];  // positions 2, 3 of the next chunk's items until their V space is free
+  auto transform_a = [&](const unsigned char* sr) {
+#pragma unroll
+    for (int it = 0; it < 4; ++it) {
+      f32x4 t[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const f32x4 a = *reinterpret_cast<const f32x4*>(sr + it * (72 * 64) + roffs[j]);
+        const f32x4 c = *reinterpret_cast<const f32x4*>(sr + it * (72 * 64) + roffs[4 + j]);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) t[j][e] = __builtin_fmaf(sg, c[e], a[e]);  // a +- c, one rounding
+      }
+      split_store(t[0] - t[2], 0, it);
+      split_store(t[1] + t[2], 1, it);
+      hold[it][0] = t[2] - t[1];
+      hold[it][1] = t[1] - t[3];
+    }
+  };
+  auto transform_b = [&]() {
+#pragma unroll
+    for (int it = 0; it < 4; ++it) {
+      split_store(hold[it][0], 2, it);
+      split_store(hold[it][1], 3, it);
+    }
+  };
+
+  f32x16 acc[16];  // [position j][tile block][channel block]
+#pragma unroll
+  for (int x = 0; x < 16; ++x)
+#pragma unroll
+    for (int q = 0; q < 16; ++q) acc[x][q] = 0.f;
+  // A fragment: rows = tiles 32 tb + r32, lane half h holds channels 8h .. 8h+7 (swz)
+  const int aoff = r32 * 32 + ((h ^ ((r32 >> 3) & 1)) << 4);
+  auto read_a = [&](int j, bf16x8 (&a)[3][2]) {
+#pragma unroll
+    for (int pl = 0; pl < 3; ++pl)
+#pragma unroll
+      for (int tb = 0; tb < 2; ++tb)
+        a[pl][tb] = *reinterpret_cast<const bf16x8*>(sv + (3 * j + pl) * kSImg + tb * 1024 + aoff);
+  };
+  auto mfmas = [&](int j, const bf16x8 (&a)[3][2], const bf16x8 (&u)[3][2]) {
+    constexpr int TA[6] = {1, 2, 0, 1, 0, 0}, TB[6] = {1, 0, 2, 0, 1, 0};
+#pragma unroll
+    for (int t = 0; t < 6; ++t)
+#pragma unroll
+      for (int tb = 0; tb < 2; ++tb)
+#pragma unroll
+        for (int cb = 0; cb < 2; ++cb)
+          acc[4 * j + 2 * tb + cb] =
+              __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[TA[t]][tb], u[TB[t]][cb], acc[4 * j + 2 * tb + cb], 0, 0, 0);
+  };
+
+  // prologue: raw(0), raw(1), U of position 0; V(0) into the private region
+  bf16x8 ua[3][2], ub[3][2], fa[3][2], fb[3][2];
+  dma_raw(0, sR0);
+  dma_raw(1, sR1);
+  load_u(0, 0, ua);
+  __builtin_amdgcn_sched_barrier(0);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  transform_a(sR0);
+  transform_b();
+  __syncthreads();  // every wave has read raw(0): chunk 0 may refill its buffer
+  // chunk k, C = k & 1: raw(k+1) is in raw buffer C ^ 1, raw(k+2) goes to buffer C
+  auto chunk = [&](int k, auto cc) {
+    constexpr int C = decltype(cc)::value;
+    dma_raw(k + 2, C ? sR1 : sR0);
+    __builtin_amdgcn_sched_barrier(0);
+    read_a(0, fa);
+    read_a(1, fb);
+    load_u(k, 1, ub);
+    mfmas(0, fa, ua);
+    transform_a(C ? sR0 : sR1);
+    load_u(k, 2, ua);
+    mfmas(1, fb, ub);
+    read_a(2, fa);
+    read_a(3, fb);
+    load_u(k, 3, ub);
+    mfmas(2, fa, ua);
+    transform_b();
+    load_u(k + 1, 0, ua);
+    mfmas(3, fb, ub);
+    // the raw DMA is older than the 24 U loads behind it and loads return in order: it has landed
+    // when at most the last six (the next chunk's position 0) are outstanding
+    __builtin_amdgcn_sched_barrier(0);
+    asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+    __syncthreads();
+  };
+  int k = 0;
+  for (; k + 1 < nck; k += 2) {
+    chunk(k, std::integral_constant<int, 0>());
+    chunk(k + 1, std::integral_constant<int, 1>());
+  }
+  if (k < nck) chunk(k, std::integral_constant<int, 0>());
+
+  // output transform: m[wave][q] of every (tile, channel) through LDS as [4 rows][64 tiles][64 co]
+  // fp32 (the V space: the last barrier is behind every wave's last fragment read), then
+  // wino4_kernel's column sums and epilogue, wave w on tiles 16w .. 16w+15, lane = channel
+  float* const ex = reinterpret_cast<float*>(sV);
+  const int co = co0 + lane;
+  const float bias = p.bias ? p.bias[co] : 0.f;
+#pragma unroll
+  for (int q = 0; q < 2; ++q) {
+    if (q) __syncthreads();
+#pragma unroll
+    for (int tb = 0; tb < 2; ++tb)
+#pragma unroll
+      for (int cb = 0; cb < 2; ++cb)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int tile = 32 * tb + (r & 3) + 8 * (r >> 2) + 4 * h;
+          const float m0 = acc[2 * tb + cb][r], m1 = acc[4 + 2 * tb + cb][r], m2 = acc[8 + 2 * tb + cb][r],
+                      m3 = acc[12 + 2 * tb + cb][r];
+          ex[(wave * kTT + tile) * kCO + 32 * cb + r32] = q ? m1 - m2 - m3 : m0 + m1 + m2;
+        }
+    __syncthreads();
+#pragma unroll 4
+    for (int t = 0; t < 16; ++t) {
+      const int tile = 16 * wave + t;
+      float m[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) m[i] = ex[(i * kTT + tile) * kCO + lane];
+      const int oy0 = 2 * (by * kT + (tile >> 3)), ox = 2 * (bx * kT + (tile & 7)) + q;
+      const float e1 = -m[2] - m[3];
+      float y0 = m[0] + m[1] + m[2] + bias;
+      float y1 = m[1] + e1 + bias;
+      if (p.relu) {
+        y0 = fmaxf(y0, 0.f);
+        y1 = fmaxf(y1, 0.f);
+      }
+      if (ox < p.Wo) {
+        const long long i0 = ((long long)(b * p.Ho + oy0) * p.Wo + ox) * p.ldc + co;
+        const long long i1 = i0 + (long long)p.Wo * p.ldc;
+        if (p.mask) {
+          if (oy0 < p.Ho && !(p.mask[i0] > 0.f)) y0 = 0.f;
+          if (oy0 + 1 < p.Ho && !(p.mask[i1] > 0.f)) y1 = 0.f;
+        }
+        if (oy0 < p.Ho) p.y[i0] = y0;
+        if (oy0 + 1 < p.Ho) p.y[i1] = y1;
+      }
+    }
+  }
+}
+
 // U = G g G^T per (co, ci) as in wino_weights_kernel, split into three bf16 planes;
 // w [Cout][3][3][Cin] -> up [Cin/16][16][3][Cout][16]
 __global__ void wino_weights_s3_kernel(const float* __restrict__ w, bf16* __restrict__ up, int Cout, int Cin) {
@@ -1243,7 +1502,10 @@ static int conv3x3_wino_launch(const float* x, const float* u, const void* up, c
     WinoS3P q;
     static_cast<WinoP&>(q) = p;
     q.up = (const bf16*)up;
-    hipLaunchKernelGGL(wino_s3_kernel, dim3(p.nblk), dim3(256), 0, (hipStream_t)s_, q);
+    if (tuning().wino_s3_rows)
+      hipLaunchKernelGGL(wino_s3_rows_kernel, dim3(p.nblk), dim3(256), 0, (hipStream_t)s_, q);
+    else
+      hipLaunchKernelGGL(wino_s3_kernel, dim3(p.nblk), dim3(256), 0, (hipStream_t)s_, q);
   } else if (tuning().wino4 && bufx) {
     hipLaunchKernelGGL(wino4_kernel<WINO4_DBG>, dim3(p.nblk), dim3(256), 0, (hipStream_t)s_, p);
   } else
