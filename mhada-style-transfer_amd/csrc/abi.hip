@@ -26,6 +26,16 @@ int check_launch(const char* what) {
   return MHADA_OK;
 }
 
+int num_cus() {
+  static int n = 0;
+  if (n == 0) {
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
+  }
+  return n;
+}
+
 namespace {
 struct Knob {
   const char* name;  // mhada_set_tuning name; env variable MHADA_<NAME upper-cased>

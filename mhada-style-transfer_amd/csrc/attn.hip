@@ -35,97 +35,6 @@
 
 namespace mhada {
 
-// Scores of keys >= Ns: -inf (softmax) / -1 (cosine: p = s + 1 = 0).
-template <int ACT, int NKB>
-MHADA_DEV void mask_tile(f32x16 (&S)[NKB], int key0, int Ns, int h) {
-#pragma unroll
-  for (int kb = 0; kb < NKB; ++kb)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int key = key0 + kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-      if (key >= Ns) S[kb][r] = (ACT == MHADA_ACT_SOFTMAX) ? -INFINITY : -1.0f;
-    }
-}
-
-// Online-softmax update of one tile: S becomes P (in place); returns true (wave-uniform)
-// when the O accumulators must be multiplied by `alpha`.  m2 is the running max in log2 units.
-template <int ACT, int NKB>
-MHADA_DEV bool softmax_tile(f32x16 (&S)[NKB], float& m2, float& l, float& alpha) {
-  float sum = 0.f;
-  if constexpr (ACT == MHADA_ACT_SOFTMAX) {
-    float mx = S[0][0];
-#pragma unroll
-    for (int kb = 0; kb < NKB; ++kb)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) mx = fmaxf(mx, S[kb][r]);
-    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-    const bool resc = __any(mx > m2 + kRescaleThr);
-    alpha = 1.f;
-    if (resc) {
-      const float mn = fmaxf(m2, mx);
-      alpha = fast_exp2(m2 - mn);
-      l *= alpha;
-      m2 = mn;
-    }
-#pragma unroll
-    for (int kb = 0; kb < NKB; ++kb)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const float pv = fast_exp2(S[kb][r] - m2);
-        S[kb][r] = pv;
-        sum += pv;
-      }
-    l += sum;
-    return resc;
-  } else {
-#pragma unroll
-    for (int kb = 0; kb < NKB; ++kb)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const float pv = S[kb][r] + 1.0f;
-        S[kb][r] = pv;
-        sum += pv;
-      }
-    l += sum;
-    alpha = 1.f;
-    return false;
-  }
-}
-
-// Tile max of the scores in log2 units, combined over the two lane halves (same query).
-template <int NKB>
-MHADA_DEV float tile_max_log2(const f32x16 (&S)[NKB]) {
-  float mx = S[0][0];
-#pragma unroll
-  for (int kb = 0; kb < NKB; ++kb)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) mx = fmaxf(mx, S[kb][r]);
-  return fmaxf(mx, __shfl_xor(mx, 32, 64));
-}
-
-// S -> P against the current running max (no rescale); accumulates the row sum.
-template <int ACT, int NKB>
-MHADA_DEV void softmax_apply(f32x16 (&S)[NKB], float m2, float& l) {
-  float sum = 0.f;
-#pragma unroll
-  for (int kb = 0; kb < NKB; ++kb)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const float pv = (ACT == MHADA_ACT_SOFTMAX) ? fast_exp2(S[kb][r] - m2) : S[kb][r] + 1.0f;
-      S[kb][r] = pv;
-      sum += pv;
-    }
-  l += sum;
-}
-
-MHADA_DEV void scale_acc(f32x16 (&O)[4], float alpha) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int e = 0; e < 16; ++e) O[i][e] *= alpha;
-}
-
-
 // In-kernel clock (MI355X_MICROARCH.md, DVFS give-back item 6), diagnostic builds only
 // (-DATTN_CLOCK, tools/attn_clock.py): thread 0 of each workgroup stamps the shader-clock and the
 // 100 MHz real-time counters before and after the key loop into a buffer of their own; no output
@@ -810,9 +719,9 @@ __global__ void __launch_bounds__(64 * NW, 1) attn_bf16_fsq_kernel(const AttnP p
     const bf16* ks = kvb + (long long)key0 * 128;
     const bf16* vs = vtb + key0;
 #pragma unroll
-    for (int i = 0; i < KPW; ++i) attn_glds16(ks + ksrc[i], kd + 512 * (KPW * wave + i));
+    for (int i = 0; i < KPW; ++i) glds16(ks + ksrc[i], kd + 512 * (KPW * wave + i));
 #pragma unroll
-    for (int i = 0; i < VPW; ++i) attn_glds16(vs + vsrc[i], vd + 512 * (VPW * wave + i));
+    for (int i = 0; i < VPW; ++i) glds16(vs + vsrc[i], vd + 512 * (VPW * wave + i));
   };
   // per-lane K row offsets (elements) of the two score tiles of a 32-key group
   int krow[2];
@@ -926,16 +835,6 @@ __global__ void __launch_bounds__(64 * NW, 1) attn_bf16_fsq_kernel(const AttnP p
 static bool attn_bf16_fixed_shift() { return tuning().attn_fixed_shift != 0; }
 static int attn_tk() { return tuning().attn_tk; }
 
-static int attn_num_cus() {
-  static int n = 0;
-  if (n == 0) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-  }
-  return n;
-}
-
 template <int NW>
 static void launch_attn(const AttnP& p, int dtype, int activation, hipStream_t s) {
   const dim3 grid(p.nblk), blk(64 * NW);
@@ -988,7 +887,7 @@ extern "C" int mhada_attn(const void* q, const void* kv, const void* vt, const f
   // blocks smaller than the CU count (B = 1 at 512^2: 128 blocks) leaves CUs idle, so it runs 4-wave
   // blocks there (one wave per SIMD instead of two, twice as many CUs covered)
   int nw = tuning().attn_waves;
-  if (nw == 0) nw = (long long)B * H * ((Nc + 255) / 256) < attn_num_cus() ? 4 : 8;
+  if (nw == 0) nw = (long long)B * H * ((Nc + 255) / 256) < num_cus() ? 4 : 8;
   p.nqb = (Nc + 32 * nw - 1) / (32 * nw);
   const long long nblk = (long long)B * H * p.nqb;
   if (nblk > (1LL << 31) - 1) return fail("mhada_attn: grid too large");

@@ -28,6 +28,110 @@ struct AttnP {
 
 MHADA_DEV float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
 
+// ---- softmax over one score tile of the 32x32 kernels: S[kb][r] = score of key 32 kb + acc_row(r, h) -------
+// Scores of keys >= Ns: -inf (softmax) / -1 (cosine: p = s + 1 = 0).
+template <int ACT, int NKB>
+MHADA_DEV void mask_tile(f32x16 (&S)[NKB], int key0, int Ns, int h) {
+#pragma unroll
+  for (int kb = 0; kb < NKB; ++kb)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int key = key0 + kb * 32 + acc_row(r, h);
+      if (key >= Ns) S[kb][r] = (ACT == MHADA_ACT_SOFTMAX) ? -INFINITY : -1.0f;
+    }
+}
+
+// Tile max of the scores in log2 units, combined over the two lane halves (same query).
+template <int NKB>
+MHADA_DEV float tile_max_log2(const f32x16 (&S)[NKB]) {
+  float mx = S[0][0];
+#pragma unroll
+  for (int kb = 0; kb < NKB; ++kb)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) mx = fmaxf(mx, S[kb][r]);
+  return fmaxf(mx, __shfl_xor(mx, 32, 64));
+}
+
+// S -> P against the current running max (no rescale); accumulates the row sum.
+template <int ACT, int NKB>
+MHADA_DEV void softmax_apply(f32x16 (&S)[NKB], float m2, float& l) {
+  float sum = 0.f;
+#pragma unroll
+  for (int kb = 0; kb < NKB; ++kb)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const float pv = (ACT == MHADA_ACT_SOFTMAX) ? fast_exp2(S[kb][r] - m2) : S[kb][r] + 1.0f;
+      S[kb][r] = pv;
+      sum += pv;
+    }
+  l += sum;
+}
+
+template <int NO>
+MHADA_DEV void scale_acc(f32x16 (&O)[NO], float alpha) {
+#pragma unroll
+  for (int i = 0; i < NO; ++i)
+#pragma unroll
+    for (int e = 0; e < 16; ++e) O[i][e] *= alpha;
+}
+
+// Online-softmax update of one tile: S becomes P (in place); returns true (wave-uniform)
+// when the O accumulators must be multiplied by `alpha`.  m2 is the running max in log2 units.
+template <int ACT, int NKB>
+MHADA_DEV bool softmax_tile(f32x16 (&S)[NKB], float& m2, float& l, float& alpha) {
+  float sum = 0.f;
+  if constexpr (ACT == MHADA_ACT_SOFTMAX) {
+    const float mx = tile_max_log2<NKB>(S);
+    const bool resc = __any(mx > m2 + kRescaleThr);
+    alpha = 1.f;
+    if (resc) {
+      const float mn = fmaxf(m2, mx);
+      alpha = fast_exp2(m2 - mn);
+      l *= alpha;
+      m2 = mn;
+    }
+#pragma unroll
+    for (int kb = 0; kb < NKB; ++kb)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const float pv = fast_exp2(S[kb][r] - m2);
+        S[kb][r] = pv;
+        sum += pv;
+      }
+    l += sum;
+    return resc;
+  } else {
+#pragma unroll
+    for (int kb = 0; kb < NKB; ++kb)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const float pv = S[kb][r] + 1.0f;
+        S[kb][r] = pv;
+        sum += pv;
+      }
+    l += sum;
+    alpha = 1.f;
+    return false;
+  }
+}
+
+// One tile's softmax step: the deferred rescale (only when the tile max outgrows the running max
+// by kRescaleThr, so P <= 2^kRescaleThr; always on the first tile, m2 = -inf), then S -> P.
+template <int ACT, int NKB, int NO>
+MHADA_DEV void softmax_step(f32x16 (&S)[NKB], f32x16 (&O)[NO], float& m2, float& l) {
+  if constexpr (ACT == MHADA_ACT_SOFTMAX) {
+    const float mx = tile_max_log2<NKB>(S);
+    if (__any(mx > m2 + kRescaleThr)) {
+      const float mn = fmaxf(m2, mx);
+      const float alpha = fast_exp2(m2 - mn);
+      l *= alpha;
+      scale_acc<NO>(O, alpha);
+      m2 = mn;
+    }
+  }
+  softmax_apply<ACT, NKB>(S, m2, l);
+}
+
 // Epilogue shared by both variants.  O[blk] holds O^T[dv][q] for dv = (r&3)+8(r>>2)+4h+32(blk&1);
 // blk 0,1: sum p v'   blk 2,3: sum p v'^2.
 template <typename T>
@@ -96,7 +200,7 @@ MHADA_DEV void attn_exact_half(const AttnP& p, const bf16* kvb, const bf16* vtb,
       S = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*reinterpret_cast<const bf16x8*>(kr + 16 * s), qf[s], S, 0, 0, 0);
 #pragma unroll
     for (int r = 0; r < 16; ++r)
-      if (key0 + (r & 3) + 8 * (r >> 2) + 4 * h >= Ns) S[r] = -INFINITY;
+      if (key0 + acc_row(r, h) >= Ns) S[r] = -INFINITY;
     return S;
   };
   float mx = -INFINITY;
@@ -128,15 +232,6 @@ MHADA_DEV void attn_exact_half(const AttnP& p, const bf16* kvb, const bf16* vtb,
         O[blk] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
             *reinterpret_cast<const bf16x8*>(vc + 16 * s + 32 * blk * (long long)p.ldt), pf[s], O[blk], 0, 0, 0);
   }
-}
-
-
-// --------------------------------------------------------------------------------------
-// LDS-DMA (global_load_lds, 16 B per lane) for the K / V'^T rings of the LDS-DMA kernels.
-// --------------------------------------------------------------------------------------
-MHADA_DEV void attn_glds16(const void* src, void* lds) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                   (__attribute__((address_space(3))) void*)lds, 16, 0, 0);
 }
 
 // Key of score row r (0..15) of tile t (0, 1) in a 32-key group of the 16x16x32 attention layout
@@ -182,12 +277,7 @@ MHADA_DEV void attn_epilogue_q(const AttnP& p, const f32x4 (&O)[2][8], const flo
         bf16* pl = reinterpret_cast<bf16*>(p.out) + ((long long)b * p.Nc + q) * C + hh * 64 + dv0;
         bf16x4 r0, r1, r2;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          r0[e] = (bf16)res[e];
-          const float d = res[e] - (float)r0[e];
-          r1[e] = (bf16)d;
-          r2[e] = (bf16)(d - (float)r1[e]);
-        }
+        for (int e = 0; e < 4; ++e) split3_into(res[e], r0, r1, r2, e);
         *reinterpret_cast<bf16x4*>(pl) = r0;
         *reinterpret_cast<bf16x4*>(pl + ps) = r1;
         *reinterpret_cast<bf16x4*>(pl + 2 * ps) = r2;

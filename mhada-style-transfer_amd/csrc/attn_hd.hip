@@ -39,71 +39,7 @@ namespace hd {
 
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 
-static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 static bool hd_width(int D) { return D == 32 || D == 128; }
-
-// Scores of keys >= Ns: -inf (softmax) / -1 (cosine: p = s + 1 = 0).
-template <int ACT, int NKB>
-MHADA_DEV void mask_tile(f32x16 (&S)[NKB], int key0, int Ns, int h) {
-#pragma unroll
-  for (int kb = 0; kb < NKB; ++kb)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int key = key0 + kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-      if (key >= Ns) S[kb][r] = (ACT == MHADA_ACT_SOFTMAX) ? -INFINITY : -1.0f;
-    }
-}
-
-// Tile max of the scores in log2 units, combined over the two lane halves (same query).
-template <int NKB>
-MHADA_DEV float tile_max_log2(const f32x16 (&S)[NKB]) {
-  float mx = S[0][0];
-#pragma unroll
-  for (int kb = 0; kb < NKB; ++kb)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) mx = fmaxf(mx, S[kb][r]);
-  return fmaxf(mx, __shfl_xor(mx, 32, 64));
-}
-
-// S -> P against the current running max (no rescale); accumulates the row sum.
-template <int ACT, int NKB>
-MHADA_DEV void softmax_apply(f32x16 (&S)[NKB], float m2, float& l) {
-  float sum = 0.f;
-#pragma unroll
-  for (int kb = 0; kb < NKB; ++kb)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const float pv = (ACT == MHADA_ACT_SOFTMAX) ? fast_exp2(S[kb][r] - m2) : S[kb][r] + 1.0f;
-      S[kb][r] = pv;
-      sum += pv;
-    }
-  l += sum;
-}
-
-template <int NO>
-MHADA_DEV void scale_acc(f32x16 (&O)[NO], float alpha) {
-#pragma unroll
-  for (int i = 0; i < NO; ++i)
-#pragma unroll
-    for (int e = 0; e < 16; ++e) O[i][e] *= alpha;
-}
-
-// One tile's softmax step: the deferred rescale (only when the tile max outgrows the running max
-// by kRescaleThr, so P <= 2^kRescaleThr; always on the first tile, m2 = -inf), then S -> P.
-template <int ACT, int NKB, int NO>
-MHADA_DEV void softmax_step(f32x16 (&S)[NKB], f32x16 (&O)[NO], float& m2, float& l) {
-  if constexpr (ACT == MHADA_ACT_SOFTMAX) {
-    const float mx = tile_max_log2<NKB>(S);
-    if (__any(mx > m2 + kRescaleThr)) {
-      const float mn = fmaxf(m2, mx);
-      const float alpha = fast_exp2(m2 - mn);
-      l *= alpha;
-      scale_acc<NO>(O, alpha);
-      m2 = mn;
-    }
-  }
-  softmax_apply<ACT, NKB>(S, m2, l);
-}
 
 // out = sqrt(max(E2 - M^2, 1e-6)) * IN(fcs) + M + v_mu for the wave's 32 queries.
 template <typename T, int D>
@@ -219,7 +155,7 @@ __global__ void __launch_bounds__(256, D == 32 ? 2 : 1) attn_hd_f32_kernel(const
     for (int kb = 0; kb < NKB; ++kb) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const float* vr = cur + (kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * h) * LR + D + r32;
+        const float* vr = cur + (kb * 32 + acc_row(r, h)) * LR + D + r32;
         const float pr = P[kb][r];
 #pragma unroll
         for (int blk = 0; blk < NB; ++blk) {
@@ -562,8 +498,8 @@ extern "C" int mhada_attn_hd(const void* q, const void* kv, const float* fcs, co
   if (!hd::hd_width(D)) return fail("mhada_attn_hd: D must be 32 or 128 (64: mhada_attn)");
   if (dtype != MHADA_F32 && dtype != MHADA_BF16) return fail("mhada_attn_hd: bad dtype");
   if (activation != MHADA_ACT_SOFTMAX && activation != MHADA_ACT_COSINE) return fail("mhada_attn_hd: bad activation");
-  if (!hd::aligned16(q) || !hd::aligned16(kv) || !hd::aligned16(fcs) || !hd::aligned16(fcs_mu) ||
-      !hd::aligned16(fcs_rstd) || !hd::aligned16(v_mu) || !hd::aligned16(out))
+  if (!aligned16(q) || !aligned16(kv) || !aligned16(fcs) || !aligned16(fcs_mu) ||
+      !aligned16(fcs_rstd) || !aligned16(v_mu) || !aligned16(out))
     return fail("mhada_attn_hd: pointers must be 16-byte aligned");
   AttnP p = {};
   p.q = q; p.kv = kv; p.fcs = fcs; p.fcs_mu = fcs_mu; p.fcs_rstd = fcs_rstd; p.v_mu = v_mu;

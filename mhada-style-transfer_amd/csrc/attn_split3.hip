@@ -45,22 +45,6 @@ constexpr int kS3Tk = 64;  // keys per tile
 // bf16 elements of one (b, h)'s plane image: K 3 * 64 * ldt, V 3 * 128 * ldt
 __host__ __device__ constexpr long long s3_image(int ldt) { return 576LL * ldt; }
 
-// Round-to-nearest three-way split (the split of mhada_layernorm BF16X3 and ops.split3_weight).
-struct Bf3 { bf16 a, b, c; };
-MHADA_DEV Bf3 split3(float x) {
-  const bf16 a = (bf16)x;
-  const float r = x - (float)a;
-  const bf16 b = (bf16)r;
-  return Bf3{a, b, (bf16)(r - (float)b)};
-}
-template <typename V>
-MHADA_DEV void split3_into(float x, V& a, V& b, V& c, int e) {
-  const Bf3 s = split3(x);
-  a[e] = s.a;
-  b[e] = s.b;
-  c[e] = s.c;
-}
-
 // kv fp32 [BH][Ns][128] (K in columns 0..63; V' is read from vt) and the fp32 vt image [BH][128][ldt]
 // (natural key order, zero padded) -> the plane image.  One workgroup per (64-key chunk, b h).
 __global__ void __launch_bounds__(256) split3_kv_kernel(const float* __restrict__ kv, const float* __restrict__ vt,
@@ -156,7 +140,7 @@ __global__ void __launch_bounds__(256) kv_proj_s3_kernel(const float* __restrict
   for (int ni = 0; ni < 2; ++ni)
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int o = 64 * ob + 32 * ni + (r & 3) + 8 * (r >> 2) + 4 * hh;
+      const int o = 64 * ob + 32 * ni + acc_row(r, hh);
       sY[o * LY + 32 * nb + r32] = acc[ni][r] + bb[o];
     }
   __syncthreads();
@@ -480,9 +464,9 @@ __global__ void __launch_bounds__(64 * NW, 1) attn_s3_kernel(const AttnP p) {
     const bf16* ks = kp + (long long)key0 * (QK32 ? 128 : 64);
     const bf16* vs = vp + key0;
 #pragma unroll
-    for (int i = 0; i < KPW; ++i) attn_glds16(ks + ksrc[i], kd + 512 * (NW * i + wave));
+    for (int i = 0; i < KPW; ++i) glds16(ks + ksrc[i], kd + 512 * (NW * i + wave));
 #pragma unroll
-    for (int i = 0; i < VPW; ++i) attn_glds16(vs + vsrc[i], vd + 512 * (NW * i + wave));
+    for (int i = 0; i < VPW; ++i) glds16(vs + vsrc[i], vd + 512 * (NW * i + wave));
   };
   int krow[2];
 #pragma unroll
@@ -689,16 +673,6 @@ __global__ void __launch_bounds__(64 * NW, 1) attn_s3_kernel(const AttnP p) {
   else attn_epilogue_q<float, PLANES>(p, O, lt, b, hh, q0, g, r16);
 }
 
-static int s3_num_cus() {
-  static int n = 0;
-  if (n == 0) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-  }
-  return n;
-}
-
 }  // namespace mhada
 
 using namespace mhada;
@@ -737,7 +711,7 @@ static int attn_split3_launch(const char* name, const float* q, const void* img,
   // waves per block as mhada_attn: tuning attn_waves, 0 = 8, or 4 when the 8-wave grid has fewer
   // blocks than CUs
   int nw = tuning().attn_waves;
-  if (nw == 0) nw = (long long)B * H * ((Nc + 255) / 256) < s3_num_cus() ? 4 : 8;
+  if (nw == 0) nw = (long long)B * H * ((Nc + 255) / 256) < num_cus() ? 4 : 8;
   p.nqb = (Nc + 32 * nw - 1) / (32 * nw);
   const long long nblk = (long long)B * H * p.nqb;
   if (nblk > (1LL << 31) - 1) return fail(std::string(name) + ": grid too large");
@@ -782,7 +756,7 @@ extern "C" int mhada_attn_train_fwd_split3(const float* q, const float* k, const
   p.ldt = (Ns + 63) / 64 * 64;
   if (384LL * p.ldt >= (1LL << 31)) return fail("mhada_attn_train_fwd_split3: Ns too large for 32-bit plane offsets");
   int nw = tuning().attn_waves;
-  if (nw == 0) nw = (long long)BH * ((Nc + 255) / 256) < s3_num_cus() ? 4 : 8;
+  if (nw == 0) nw = (long long)BH * ((Nc + 255) / 256) < num_cus() ? 4 : 8;
   p.nqb = (Nc + 32 * nw - 1) / (32 * nw);
   const long long nblk = (long long)BH * p.nqb;
   if (nblk > (1LL << 31) - 1) return fail("mhada_attn_train_fwd_split3: grid too large");

@@ -61,10 +61,6 @@ constexpr int min_waves(int D, Kind kind) { return D == 32 ? 2 : D == 128 ? 1 : 
 // dK/dV': V'^2 of the wave's keys kept in registers, or (the budget at 128) squared at the operand
 constexpr bool keep_v2(int D) { return D <= 64; }
 
-MHADA_DEV int acc_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
-
-MHADA_DEV f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
-MHADA_DEV void st4(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
 MHADA_DEV f32x16 mfma(float a, float b, const f32x16& c) {
   return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
 }
@@ -106,16 +102,6 @@ __device__ unsigned long long g_train_clock[4 * kTrainClockBlocks];
   do {                    \
   } while (0)
 #endif
-
-// Workgroup barrier for the LDS hand-off only: __syncthreads() also acts as a release fence
-// that drains every outstanding global store (vmcnt counts stores on CDNA4), which would
-// serialise the dS spill stores with the next tile.
-MHADA_DEV void lds_barrier() {
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_sched_barrier(0);
-}
 
 // Register-staged copy of rows [r0, r0+TT) of a [n][W] matrix (zero rows past n; with CLAMP, r0
 // may lie past n) into an LDS tile of rows padded to W + 4 floats (row reads by ds_read_b128 and
@@ -500,7 +486,7 @@ __global__ void __launch_bounds__(kNT, min_waves(D, DKV)) attn_train_dkv_kernel(
 #pragma unroll
       for (int r = 0; r < 16; ++r)
         __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(dS[r]), dsr,
-                                              (int)(base + ((r & 3) + 8 * (r >> 2)) * p.Ns * 4u), 0, 0);
+                                              (int)(base + acc_row(r, 0) * p.Ns * 4u), 0, 0);
     }
     // G1^T, G2^T (c x keys) += [dM' | dE2']^T (c x queries) . P;  dK^T += Q^T . dS
 #pragma unroll
@@ -543,8 +529,7 @@ __global__ void __launch_bounds__(kNT, min_waves(D, DKV)) attn_train_dkv_kernel(
 // ---------------------------------------------------------------------------------------
 MHADA_DEV void train_glds(const float* src, float* lds, int bytes) {
   if (bytes == 16)
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                     (__attribute__((address_space(3))) void*)lds, 16, 0, 0);
+    glds16(src, lds);
   else
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
                                      (__attribute__((address_space(3))) void*)lds, 4, 0, 0);
@@ -677,7 +662,7 @@ __global__ void __launch_bounds__(256, 1) attn_train_dkv_dma_kernel(const TrainP
     const float* sQ = smem + sl * SLOT;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int j = r & 3, rowb = (r & 3) + 8 * (r >> 2), b3 = (r >> 2) & 1;
+      const int j = r & 3, rowb = acc_row(r, 0), b3 = (r >> 2) & 1;
       const float* o = sQ + xo[j] + rowb * 128;
       const float* qq = sQ + xq[j] + rowb * 64;
       G1[0] = mfma(o[32 * b3], P[r], G1[0]);

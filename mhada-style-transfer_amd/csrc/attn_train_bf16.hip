@@ -49,9 +49,6 @@ constexpr float kLog2e = 1.4426950408889634f;
 constexpr int kNW = 4;        // waves per workgroup: 128 queries (fwd, dQ) or keys (dK/dV')
 constexpr int NT = 64 * kNW;  // threads per workgroup
 
-MHADA_DEV int acc_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
-MHADA_DEV f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
-MHADA_DEV void st4(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
 MHADA_DEV bf16x8 ld8(const bf16* p) { return *reinterpret_cast<const bf16x8*>(p); }
 MHADA_DEV f32x16 mfma(bf16x8 a, bf16x8 b, const f32x16& c) {
   return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
@@ -89,14 +86,6 @@ struct TrainBfP {
   float* dv;         // [BH][Ns][64]
   int Nc, Ns, NcP, NsP, nb, nblk;  // NxP = ceil64(Nx); nb = row blocks per (b, h)
 };
-
-// LDS hand-off barrier (attn_train.hip): waits for the LDS operations only.
-MHADA_DEV void lds_barrier() {
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_sched_barrier(0);
-}
 
 // Register-staged copy of the ROWS x COLS bf16 tile at (r0, c0) of a [nrows][ld] matrix (rows past
 // nrows zero; the columns must exist) into an LDS tile of rows padded to COLS + 8 elements (16-byte

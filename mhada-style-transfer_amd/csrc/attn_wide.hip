@@ -160,7 +160,7 @@ __global__ void __launch_bounds__(NT) attn_wide_kernel(const WideP p) {
     float mx = -INFINITY;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      S[r] = (r & 3) + 8 * (r >> 2) < nvalid ? S[r] : -INFINITY;
+      S[r] = acc_row(r, 0) < nvalid ? S[r] : -INFINITY;
       mx = fmaxf(mx, S[r]);
     }
     mx = fmaxf(mx, __shfl_xor(mx, 32, 64));

@@ -83,6 +83,25 @@ MHADA_DEV _Float16 half2_plane(float v) {
   return fabsf((float)q) < 6.103515625e-05f ? (_Float16)0.0f : q;
 }
 
+// the three bf16 planes of the SPLIT3 operands, x = a + b + c (ops.split3_weight's arithmetic, shared by
+// every plane writer): a = bf16(x), b = bf16(x - a), c = bf16(x - a - b), each round to nearest.  This is
+// THE split: every SPLIT3 product assumes that every writer of planes rounds exactly this way.
+struct Bf3 { bf16 a, b, c; };
+MHADA_DEV Bf3 split3(float x) {
+  const bf16 a = (bf16)x;
+  const float r = x - (float)a;
+  const bf16 b = (bf16)r;
+  return Bf3{a, b, (bf16)(r - (float)b)};
+}
+// element e of three plane vectors
+template <typename V>
+MHADA_DEV void split3_into(float x, V& a, V& b, V& c, int e) {
+  const Bf3 s = split3(x);
+  a[e] = s.a;
+  b[e] = s.b;
+  c[e] = s.c;
+}
+
 // 16-byte vector of T: 4 f32 or 8 bf16
 template <typename T> struct Vec16;
 template <> struct Vec16<float> { typedef f32x4 type; static constexpr int N = 4; };
@@ -134,6 +153,42 @@ MHADA_DEV float wave_max(float v) {
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
   return v;
 }
+
+// ---- MFMA, LDS and addressing helpers -----------------------------------------------------
+// Row of register r (0..15) of a 32x32 MFMA accumulator in lane half h (lane >> 5); the column is lane & 31.
+MHADA_DEV int acc_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
+
+MHADA_DEV f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
+MHADA_DEV void st4(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
+
+// Workgroup barrier for an LDS hand-off only: __syncthreads() also acts as a release fence that drains
+// every outstanding global store (vmcnt counts stores on CDNA4), which would serialise a kernel's
+// stores with its next tile.
+MHADA_DEV void lds_barrier() {
+  __builtin_amdgcn_sched_barrier(0);
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  __builtin_amdgcn_s_barrier();
+  __builtin_amdgcn_sched_barrier(0);
+}
+
+// LDS-DMA (global_load_lds), 16 B per lane: lane l's 16 bytes at src land at lds + 16 l
+MHADA_DEV void glds16(const void* src, void* lds) {
+  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
+                                   (__attribute__((address_space(3))) void*)lds, 16, 0, 0);
+}
+
+// reflect padding of index i into [0, n): one fold (|overhang| < n), and the same clamped for tile halos
+// that reach further out than one fold covers
+MHADA_DEV int reflect1(int i, int n) { return i < 0 ? -i : (i >= n ? 2 * n - 2 - i : i); }
+MHADA_DEV int reflect_clamp(int v, int n) {
+  v = v < 0 ? -v : (v >= n ? 2 * n - 2 - v : v);
+  return min(max(v, 0), n - 1);
+}
+
+inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+// compute units of the current device (abi.hip): queried once per process, 256 if the query fails
+int num_cus();
 
 // Bijective XCD-aware block remap (cdna_hip_programming.md §5 "XCD swizzle must be
 // bijective"): blocks b, b+8, b+16 ... are dealt to one XCD; give each XCD a contiguous

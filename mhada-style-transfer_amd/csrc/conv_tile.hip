@@ -42,19 +42,6 @@ constexpr int kPB = kPBY * kPBX * 8;                  // (block, 8-channel chunk
 // 128-B rows: 16 consecutive rows (a ds_read_b128 cycle) must hit 16 distinct 16-B bank
 // groups = 8 * (row & 1) + chunk', hence chunk' = chunk ^ ((row >> 1) & 7)
 MHADA_DEV int swz(int row, int chunk) { return row * 64 + ((chunk ^ ((row >> 1) & 7)) << 3); }
-// Workgroup barrier for LDS hand-offs only.  __syncthreads() is a release fence as well, which
-// makes every wave drain its outstanding GLOBAL stores (vmcnt(0) counts stores on CDNA4) before
-// the barrier: the tile's 16 epilogue stores per lane would then serialise with the next tile.
-MHADA_DEV void lds_barrier() {
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_sched_barrier(0);
-}
-MHADA_DEV int reflect_clamp(int v, int n) {
-  v = v < 0 ? -v : (v >= n ? 2 * n - 2 - v : v);
-  return min(max(v, 0), n - 1);
-}
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 

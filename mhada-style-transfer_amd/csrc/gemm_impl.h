@@ -98,8 +98,6 @@ MHADA_DEV void store_chunk(TC* dst, const float (&f)[Cfg<TC>::E]) {
   *reinterpret_cast<typename Vec16<TC>::type*>(dst) = v;
 }
 
-MHADA_DEV int reflect1(int i, int n) { return i < 0 ? -i : (i >= n ? 2 * n - 2 - i : i); }
-
 // 16 zero bytes per lane for LDS-DMA staging of zero-padding taps (a glds cannot write zeros)
 static __device__ __attribute__((aligned(16))) float g_zero16[4];
 
@@ -792,11 +790,6 @@ __global__ void __launch_bounds__(64 * WM * WN) gemm_kernel(const GemmP p) {
 // operand groups).  Waits are counted (vmcnt 4/0), never a drain inside the loop; the phase
 // schedule and ring-slot reuse rules are spelled out above the main loop.
 // ------------------------------------------------------------------------------------
-MHADA_DEV void glds16(const void* src, void* lds) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                   (__attribute__((address_space(3))) void*)lds, 16, 0, 0);
-}
-
 #define PP_BARRIER() do { __builtin_amdgcn_sched_barrier(0); __builtin_amdgcn_s_barrier(); __builtin_amdgcn_sched_barrier(0); } while (0)
 #define PP_LGKM0() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
 
@@ -1855,18 +1848,6 @@ __global__ void __launch_bounds__(BM * 2) gemm_n64_kernel(const GemmP p) {
         acc[0][n] = __builtin_amdgcn_mfma_f32_32x32x2f32(wf[n][s >> 2][s & 3], af[s >> 2][s & 3], acc[0][n], 0, 0, 0);
   }
   store_tile<float, 1, 2>(p, acc, z1, z2, m0 + 32 * wave + r32, 0, h);
-}
-
-static bool aligned16(const void* ptr) { return ((uintptr_t)ptr & 15) == 0; }
-
-static int num_cus() {
-  static int n = 0;
-  if (!n) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-  }
-  return n;
 }
 
 // tuning gemm_persist = 0 selects the one-shot ping-pong kernel (A/B runs)

@@ -35,11 +35,6 @@
 namespace mhada {
 namespace {
 
-MHADA_DEV void n64s3_glds16(const void* src, void* lds) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                   (__attribute__((address_space(3))) void*)lds, 16, 0, 0);
-}
-
 #define N64S3_BARRIER() do { __builtin_amdgcn_sched_barrier(0); __builtin_amdgcn_s_barrier(); __builtin_amdgcn_sched_barrier(0); } while (0)
 
 struct N64S3P {
@@ -57,15 +52,7 @@ constexpr int kSlotBytes = kAH * 4 + kWH * 2;
 
 MHADA_DEV void split8(const f32x4& lo, const f32x4& hi, bf16x8& p0, bf16x8& p1, bf16x8& p2) {
 #pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const float x = j < 4 ? lo[j] : hi[j - 4];
-    const bf16 a = (bf16)x;
-    const float r = x - (float)a;
-    const bf16 b = (bf16)r;
-    p0[j] = a;
-    p1[j] = b;
-    p2[j] = (bf16)(r - (float)b);
-  }
+  for (int j = 0; j < 8; ++j) split3_into(j < 4 ? lo[j] : hi[j - 4], p0, p1, p2, j);
 }
 
 template <int I>
@@ -118,9 +105,9 @@ __global__ void __launch_bounds__(512, 1) gemm_n64_split3_kernel(const N64S3P p)
     bf16* dw = reinterpret_cast<bf16*>(base + kAH * 4);
     const int k0 = kt * kBK;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) n64s3_glds16(asrc[i] + k0, da + (32 * wave + 8 * i) * kBK);
+    for (int i = 0; i < 4; ++i) glds16(asrc[i] + k0, da + (32 * wave + 8 * i) * kBK);
 #pragma unroll
-    for (int i = 0; i < 2; ++i) n64s3_glds16(wsrc[i] + k0, dw + 16 * (2 * wave + i) * kBK);
+    for (int i = 0; i < 2; ++i) glds16(wsrc[i] + k0, dw + 16 * (2 * wave + i) * kBK);
   };
   const int h = lane >> 5, r32 = lane & 31;
   const int arow = 32 * wave + r32, asw = (arow >> 1) & 7;
@@ -225,23 +212,13 @@ __global__ void __launch_bounds__(256) transpose64_split3_kernel(const float* __
     const int idx = tid + 256 * i, d = idx >> 3, r8 = idx & 7;
     bf16x8 p0, p1, p2;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const float x = tile[(8 * r8 + j) * 65 + d];
-      const bf16 a = (bf16)x;
-      const float r = x - (float)a;
-      const bf16 b = (bf16)r;
-      p0[j] = a;
-      p1[j] = b;
-      p2[j] = (bf16)(r - (float)b);
-    }
+    for (int j = 0; j < 8; ++j) split3_into(tile[(8 * r8 + j) * 65 + d], p0, p1, p2, j);
     bf16* o = dst + ((long long)z * 64 + d) * ldt + n0 + 8 * r8;
     *reinterpret_cast<bf16x8*>(o) = p0;
     *reinterpret_cast<bf16x8*>(o + wps) = p1;
     *reinterpret_cast<bf16x8*>(o + 2 * wps) = p2;
   }
 }
-
-bool al16(const void* ptr) { return ((uintptr_t)ptr & 15) == 0; }
 
 }  // namespace
 }  // namespace mhada
@@ -254,7 +231,7 @@ extern "C" int mhada_gemm_n64_split3(const float* a, const void* w_planes, float
   if (!a || !w_planes || !c || nz <= 0 || nz > 65535 || M <= 0 || K <= 0)
     return fail("mhada_gemm_n64_split3: bad args");
   if (K % kBK || lda < K || ldw < K || ldc < 64 || lda % 4 || sa % 4 || ldw % 8 || sw % 8 || wps % 8 || ldc % 4 ||
-      sc % 4 || !al16(a) || !al16(w_planes) || !al16(c))
+      sc % 4 || !aligned16(a) || !aligned16(w_planes) || !aligned16(c))
     return fail("mhada_gemm_n64_split3: needs K % 32 == 0, 16-byte aligned rows and problems");
   if ((long long)(M - 1) * lda + K >= (1LL << 31) || 2 * wps + 63LL * ldw + K >= (1LL << 31))
     return fail("mhada_gemm_n64_split3: operand spans need 32-bit element offsets per problem");
@@ -271,7 +248,7 @@ extern "C" int mhada_gemm_n64_split3(const float* a, const void* w_planes, float
 extern "C" int mhada_transpose64_split3(const float* src, void* planes, int BH, int N, int ldt, mhada_stream_t s_) {
   if (!src || !planes || BH <= 0 || BH > 65535 || N <= 0 || ldt < N || ldt % 64)
     return fail("mhada_transpose64_split3: bad args (ldt % 64 == 0, ldt >= N)");
-  if (!al16(src) || !al16(planes)) return fail("mhada_transpose64_split3: 16-byte aligned operands");
+  if (!aligned16(src) || !aligned16(planes)) return fail("mhada_transpose64_split3: 16-byte aligned operands");
   const long long wps = (long long)BH * 64 * ldt;
   hipLaunchKernelGGL(transpose64_split3_kernel, dim3(ldt / 64, BH), dim3(256), 0, (hipStream_t)s_, src,
                      reinterpret_cast<bf16*>(planes), N, ldt, wps);

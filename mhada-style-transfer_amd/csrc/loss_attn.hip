@@ -113,7 +113,7 @@ __global__ void __launch_bounds__(64 * W) loss_attn_kernel(const LossAttnP p) {
     float vv[16][NB];
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int key = min(key0 + (r & 3) + 8 * (r >> 2) + 4 * h, p.Ns - 1);
+      const int key = min(key0 + acc_row(r, h), p.Ns - 1);
 #pragma unroll
       for (int j = 0; j < NB; ++j) vv[r][j] = vb[(long long)key * p.Dv + 32 * j + r32];
     }
@@ -131,7 +131,7 @@ __global__ void __launch_bounds__(64 * W) loss_attn_kernel(const LossAttnP p) {
       float mx = -INFINITY;
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int key = key0 + (r & 3) + 8 * (r >> 2) + 4 * h;
+        const int key = key0 + acc_row(r, h);
         if (key0 + 32 > p.Ns && key >= p.Ns) S[r] = -INFINITY;  // uniform test first: tail tile only
         mx = fmaxf(mx, S[r]);
       }
@@ -160,7 +160,7 @@ __global__ void __launch_bounds__(64 * W) loss_attn_kernel(const LossAttnP p) {
       float sum = 0.f;
 #pragma unroll
       for (int r = 0; r < 16; ++r) {  // rows arrive unit-normalised: s = q.k/(|q||k|) + 1
-        const int key = key0 + (r & 3) + 8 * (r >> 2) + 4 * h;
+        const int key = key0 + acc_row(r, h);
         S[r] = key < p.Ns ? S[r] + 1.0f : 0.f;
         sum += S[r];
       }
@@ -341,7 +341,7 @@ __global__ void __launch_bounds__(512) loss_attn_lds_kernel(const LossAttnP p) {
       if (key0 + 32 > p.Ns) {  // uniform: tail tile only
 #pragma unroll
         for (int r = 0; r < 16; ++r)
-          if (key0 + (r & 3) + 8 * (r >> 2) + 4 * h >= p.Ns) S[r] = -INFINITY;
+          if (key0 + acc_row(r, h) >= p.Ns) S[r] = -INFINITY;
       }
       float mx = -INFINITY;
 #pragma unroll
@@ -377,7 +377,7 @@ __global__ void __launch_bounds__(512) loss_attn_lds_kernel(const LossAttnP p) {
     // ---- O^T[dv][q] += V^T P^T and (V^2)^T P^T, V from LDS
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const float* vr = sV + ((r & 3) + 8 * (r >> 2) + 4 * h) * VLD + ws * 64 + r32;
+      const float* vr = sV + acc_row(r, h) * VLD + ws * 64 + r32;
 #pragma unroll
       for (int j = 0; j < NB; ++j) {
         const float vx = vr[32 * j];

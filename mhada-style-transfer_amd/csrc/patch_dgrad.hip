@@ -34,9 +34,6 @@ static_assert(kKC * 192 / 4 == kWF4 * 256, "W chunk must divide over the workgro
 static_assert(kKC * kTok / 4 <= 256, "dy chunk: at most one float4 per thread");
 static_assert(24 * kLDO <= 2 * kKC * kLDW, "the output tile reuses the W buffers");
 
-MHADA_DEV f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
-MHADA_DEV void st4(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
-
 __global__ void __launch_bounds__(256) patch_embed_dgrad_kernel(const float* __restrict__ dy, const float* __restrict__ w,
                                                                 float* __restrict__ dimg, int C, int H, int W, int hp,
                                                                 int wp, int strips) {
@@ -124,8 +121,6 @@ __global__ void __launch_bounds__(256) patch_embed_dgrad_kernel(const float* __r
   }
 }
 
-bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 }  // namespace
 }  // namespace mhada
 
@@ -137,7 +132,7 @@ extern "C" int mhada_patch_embed_dgrad(const float* dy, const float* w, float* d
   if (Ci != 3) return fail("mhada_patch_embed_dgrad: Ci must be 3 (an RGB image)");
   if (C <= 0 || C % 64) return fail("mhada_patch_embed_dgrad: C must be a positive multiple of 64");
   if (H < 8 || W < 8 || W % 8) return fail("mhada_patch_embed_dgrad: H >= 8 and W a positive multiple of 8");
-  if (!al16(dy) || !al16(w) || !al16(dimg)) return fail("mhada_patch_embed_dgrad: dy / w / dimg must be 16-byte aligned");
+  if (!aligned16(dy) || !aligned16(w) || !aligned16(dimg)) return fail("mhada_patch_embed_dgrad: dy / w / dimg must be 16-byte aligned");
   const int hp = H / 8, wp = W / 8, strips = (wp + kTok - 1) / kTok;
   // 32-bit element offsets in the kernel
   if ((long long)B * hp * wp * C >= (1LL << 31) || (long long)B * 3 * H * W >= (1LL << 31))

@@ -342,14 +342,12 @@ __global__ void __launch_bounds__(1024) out3_wgrad_finish_kernel(const float* __
   }
 }
 
-bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 }  // namespace
 
 extern "C" int mhada_vgg_stem_dgrad(const float* dy, const float* y, const float* wd, float* dimg, int B, int H, int W,
                                     mhada_stream_t s_) {
   if (!dy || !y || !wd || !dimg || B <= 0 || H <= 0 || W <= 0) return fail("mhada_vgg_stem_dgrad: bad args");
-  if (!al16(dy) || !al16(y)) return fail("mhada_vgg_stem_dgrad: dy / y must be 16-byte aligned");
+  if (!aligned16(dy) || !aligned16(y)) return fail("mhada_vgg_stem_dgrad: dy / y must be 16-byte aligned");
   if ((long long)B * H * W * 64 >= (1LL << 40)) return fail("mhada_vgg_stem_dgrad: too large");
   const int tiles_x = (W + 63) / 64, strips_y = (H + 4 * kStemRows - 1) / (4 * kStemRows);
   const long long nb = (long long)B * strips_y * tiles_x;
@@ -362,7 +360,7 @@ extern "C" int mhada_vgg_stem_dgrad(const float* dy, const float* y, const float
 extern "C" int mhada_out3_dgrad(const float* dy, const float* y, const float* wd, const float* relu_x, float* dx, int B,
                                 int H, int W, mhada_stream_t s_) {
   if (!dy || !y || !wd || !dx || B <= 0 || H < 2 || W < 2) return fail("mhada_out3_dgrad: bad args (H, W >= 2)");
-  if (!al16(dx) || !al16(relu_x)) return fail("mhada_out3_dgrad: dx / relu_x must be 16-byte aligned");
+  if (!aligned16(dx) || !aligned16(relu_x)) return fail("mhada_out3_dgrad: dx / relu_x must be 16-byte aligned");
   const int tiles_x = (W + 63) / 64, tiles_y = (H + 3) / 4;
   const long long nb = (long long)B * tiles_x * tiles_y;
   if (nb >= (1LL << 31)) return fail("mhada_out3_dgrad: grid too large");

@@ -64,12 +64,10 @@ __global__ void __launch_bounds__(256) layernorm_kernel(const float* __restrict_
         yr[c] = hi;
         yr[plane + c] = half2_plane(sv - (float)hi);
       } else if constexpr (FORM == 1) {  // three bf16 planes: val = p0 + p1 + p2 to 2^-25 (the SPLIT3 GEMM operand)
-        const bf16 p0 = (bf16)val;
-        const float r1 = val - (float)p0;
-        const bf16 p1 = (bf16)r1;
-        yr[c] = p0;
-        yr[plane + c] = p1;
-        yr[2 * plane + c] = (bf16)(r1 - (float)p1);
+        const Bf3 s = split3(val);
+        yr[c] = s.a;
+        yr[plane + c] = s.b;
+        yr[2 * plane + c] = s.c;
       } else {
         yr[c] = from_f32<TO>(val);
       }
@@ -271,12 +269,10 @@ MHADA_DEV void vit_batch_attn_small_body(const T* __restrict__ qkv, void* __rest
       pl[pstride] = half2_plane(v - (float)hi);
     } else if constexpr (PLANES == 1) {
       bf16* pl = reinterpret_cast<bf16*>(out_) + at;
-      const bf16 a = (bf16)o;
-      const float r1 = o - (float)a;
-      const bf16 b = (bf16)r1;
-      pl[0] = a;
-      pl[pstride] = b;
-      pl[2 * pstride] = (bf16)(r1 - (float)b);
+      const Bf3 s = split3(o);
+      pl[0] = s.a;
+      pl[pstride] = s.b;
+      pl[2 * pstride] = s.c;
     } else {
       reinterpret_cast<T*>(out_)[at] = from_f32<T>(o);
     }
@@ -316,12 +312,7 @@ __global__ void __launch_bounds__(256) vit_batch_copy_v_s3_kernel(const float* _
   const f32x4 v = *reinterpret_cast<const f32x4*>(qkv + 4 * (n * 3 * row4 + 2 * row4 + c));
   bf16x4 a, b, d;
 #pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    a[e] = (bf16)v[e];
-    const float r = v[e] - (float)a[e];
-    b[e] = (bf16)r;
-    d[e] = (bf16)(r - (float)b[e]);
-  }
+  for (int e = 0; e < 4; ++e) split3_into(v[e], a, b, d, e);
   bf16* pl = planes + 4 * idx;
   *reinterpret_cast<bf16x4*>(pl) = a;
   *reinterpret_cast<bf16x4*>(pl + pstride) = b;
@@ -913,8 +904,6 @@ __global__ void __launch_bounds__(256) upsample2x_vec_kernel(const T* __restrict
   }
 }
 
-static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 // fp32 [n] -> three bf16 planes [3][n] (p0 = bf16(x), p1 = bf16(x - p0), p2 = bf16(x - p0 - p1), the
 // SPLIT3 GEMM operand); four elements per thread, n % 4 == 0, 16-B aligned.
 __global__ void __launch_bounds__(256) split3_rows_kernel(const float* __restrict__ x, bf16* __restrict__ y,
@@ -924,12 +913,7 @@ __global__ void __launch_bounds__(256) split3_rows_kernel(const float* __restric
   const f32x4 v = *reinterpret_cast<const f32x4*>(x + i);
   bf16x4 a, b, c;
 #pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    a[e] = (bf16)v[e];
-    const float r = v[e] - (float)a[e];
-    b[e] = (bf16)r;
-    c[e] = (bf16)(r - (float)b[e]);
-  }
+  for (int e = 0; e < 4; ++e) split3_into(v[e], a, b, c, e);
   *reinterpret_cast<bf16x4*>(y + i) = a;
   *reinterpret_cast<bf16x4*>(y + n + i) = b;
   *reinterpret_cast<bf16x4*>(y + 2 * n + i) = c;
@@ -944,10 +928,8 @@ __global__ void __launch_bounds__(256) split3_weight_kernel(const float* __restr
   if (i >= (long long)N * K0) return;
   const int n = (int)(i / K0), k = (int)(i - (long long)n * K0);
   const float x = transposed ? w[(long long)k * N + n] : w[i];
-  const bf16 q0 = (bf16)x;
-  const float r = x - (float)q0;
-  const bf16 q1 = (bf16)r;
-  const bf16 q2 = (bf16)(r - (float)q1);
+  const Bf3 s = split3(x);
+  const bf16 q0 = s.a, q1 = s.b, q2 = s.c;
   bf16* o = out + (long long)n * 6 * K0 + 6 * 64 * (k >> 6) + (k & 63);
   o[0] = q1;
   o[64] = q0;

@@ -57,8 +57,6 @@ struct TnP {
 
 constexpr int kTnBN = 128, kTnBK = 32;
 
-MHADA_DEV int tn_reflect(int i, int n) { return i < 0 ? -i : (i >= n ? 2 * n - 2 - i : i); }
-
 // BMODE: MHADA_A_ROWS, MHADA_A_CONV3X3 (reflect pad 1), MHADA_A_CONV3X3_ZERO (zero pad `pad`),
 // MHADA_A_PATCH8 (k = token (b, py, px) of the 8x8 / stride-8 patch grid, n = c*64 + ky*8 + kx
 // of an NCHW image [B][img_c][img_h][img_w]: the patch-embedding weight gradient).
@@ -196,8 +194,8 @@ __global__ void __launch_bounds__(256, 2) gemm_tn_kernel(const TnP p) {
             X = ox + tap_dx + 1 - p.pad;
             ok = Y >= 0 && Y < p.img_h && X >= 0 && X < p.img_w;
           } else {
-            Y = tn_reflect(oy + tap_dy, p.img_h);
-            X = tn_reflect(ox + tap_dx, p.img_w);
+            Y = reflect1(oy + tap_dy, p.img_h);
+            X = reflect1(ox + tap_dx, p.img_w);
           }
           src = (((long long)bb * p.img_h + Y) * p.img_w + X) * p.img_c + ci;
         }
@@ -363,8 +361,8 @@ __global__ void __launch_bounds__(256) tn_skinny_kernel(const TnP p) {
           X = ox + tap_dx + 1 - p.pad;
           ok = Y >= 0 && Y < p.img_h && X >= 0 && X < p.img_w;
         } else {
-          Y = tn_reflect(oy + tap_dy, p.img_h);
-          X = tn_reflect(ox + tap_dx, p.img_w);
+          Y = reflect1(oy + tap_dy, p.img_h);
+          X = reflect1(ox + tap_dx, p.img_w);
         }
         bv = ok ? *reinterpret_cast<const f32x4*>(p.b + (((long long)bb * p.img_h + Y) * p.img_w + X) * p.img_c + ci)
                 : f32x4{0.f, 0.f, 0.f, 0.f};
@@ -417,8 +415,8 @@ __global__ void __launch_bounds__(256) tn_skinny_lds_kernel(const TnP p, int nti
       if constexpr (BMODE == MHADA_A_CONV3X3_ZERO) {
         ok = Y >= 0 && Y < p.img_h && X >= 0 && X < p.img_w;
       } else {
-        Y = tn_reflect(Y, p.img_h);
-        X = tn_reflect(X, p.img_w);
+        Y = reflect1(Y, p.img_h);
+        X = reflect1(X, p.img_w);
       }
       Y = min(max(Y, 0), p.img_h - 1);  // rows / columns past a ragged tile edge feed no pixel
       X = min(max(X, 0), p.img_w - 1);
@@ -552,14 +550,7 @@ __global__ void __launch_bounds__(256) ln_fwd_train_kernel(const float* __restri
       const long long ps = (long long)rows * COLS;
       bf16x4 p0, p1, p2;
 #pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const bf16 a = (bf16)o[e];
-        const float r = o[e] - (float)a;
-        const bf16 q = (bf16)r;
-        p0[e] = a;
-        p1[e] = q;
-        p2[e] = (bf16)(r - (float)q);
-      }
+      for (int e = 0; e < 4; ++e) split3_into(o[e], p0, p1, p2, e);
       bf16* pr = planes + (long long)row * COLS + c;
       *reinterpret_cast<bf16x4*>(pr) = p0;
       *reinterpret_cast<bf16x4*>(pr + ps) = p1;
@@ -1049,12 +1040,10 @@ __global__ void __launch_bounds__(256) vgg_input_bwd_kernel(const float* __restr
 // planes (round 6, may be null): dqkv's three bf16 planes as well, plane stride pstride elements from
 // the dqkv base of this call — the QKV input-gradient GEMM's SPLIT3 operand (train_fns plane hand-off).
 MHADA_DEV void store_split3(bf16* p, long long ps, float x) {
-  const bf16 a = (bf16)x;
-  const float r = x - (float)a;
-  const bf16 b = (bf16)r;
-  p[0] = a;
-  p[ps] = b;
-  p[2 * ps] = (bf16)(r - (float)b);
+  const Bf3 s = split3(x);
+  p[0] = s.a;
+  p[ps] = s.b;
+  p[2 * ps] = s.c;
 }
 
 __global__ void __launch_bounds__(256) vit_batch_attn_bwd_kernel(const float* __restrict__ qkv,
@@ -1139,7 +1128,6 @@ __global__ void __launch_bounds__(256) vit_batch_attn_bwd_kernel(const float* __
   }
 }
 
-static bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 static dim3 grid1(long long n) { return dim3((unsigned)((n + 255) / 256)); }
 
 }  // namespace mhada
@@ -1156,7 +1144,7 @@ extern "C" int mhada_gemm_tn(const mhada_gemm_tn_args* a, float* work, long long
   const hipStream_t s = (hipStream_t)s_;
   if (a->M <= 0 || a->N <= 0 || a->K <= 0) return fail("mhada_gemm_tn: bad sizes");
   if (a->N % 4) return fail("mhada_gemm_tn: N must be a multiple of 4");
-  if (!al16(work) || !al16(a->b)) return fail("mhada_gemm_tn: B and the workspace must be 16-byte aligned");
+  if (!aligned16(work) || !aligned16(a->b)) return fail("mhada_gemm_tn: B and the workspace must be 16-byte aligned");
   if (a->ldc < a->N) return fail("mhada_gemm_tn: ldc < N");
   TnP p{};
   p.M = a->M; p.N = a->N; p.K = a->K;
@@ -1168,7 +1156,7 @@ extern "C" int mhada_gemm_tn(const mhada_gemm_tn_args* a, float* work, long long
   if (p.nb > 1 && (a->b_mode != MHADA_A_ROWS || a->M <= 4 || a->ldc != a->N || (a->sza | a->szb) % 4))
     return fail("mhada_gemm_tn: batched form needs ROWS mode, M > 4, ldc == N, 16-B batch strides");
   if (p.nb > 65535) return fail("mhada_gemm_tn: batch too large");
-  const bool vec_a = al16(a->a) && a->lda % 4 == 0 && a->M % 4 == 0;
+  const bool vec_a = aligned16(a->a) && a->lda % 4 == 0 && a->M % 4 == 0;
   // per-stage buffer resources: 32 rows of A / B and the out-of-range offset must stay below 2^31 bytes
   p.rsrc = vec_a && a->b_mode == MHADA_A_ROWS && (long long)kTnBK * std::max(a->lda, a->ldb) * 4 < 0x7ff00000LL &&
            (long long)kTnBK * std::max(a->lda, a->ldb) * 4 <= 0x7fffffffLL;
@@ -1214,7 +1202,7 @@ extern "C" int mhada_gemm_tn(const mhada_gemm_tn_args* a, float* work, long long
   const dim3 gsk((unsigned)S, (unsigned)((p.N / 4 + 255) / 256));
   // the 3-channel layer (M <= 4, 3x3 conv, Cin % 64 == 0, dY rows of 4 floats): LDS-tiled kernel
   if (p.M <= 4 && (a->b_mode == MHADA_A_CONV3X3 || a->b_mode == MHADA_A_CONV3X3_ZERO) && p.img_c % 64 == 0 &&
-      a->lda == 4 && al16(a->a) && tuning().tn_skinny_lds) {
+      a->lda == 4 && aligned16(a->a) && tuning().tn_skinny_lds) {
     const int ntx = (p.out_w + kSkTX - 1) / kSkTX, nty = (p.out_h + kSkTY - 1) / kSkTY;
     const long long nt = (long long)(p.K / (p.out_h * p.out_w)) * ntx * nty;
     if (nt < (1LL << 31)) {
@@ -1266,14 +1254,14 @@ extern "C" int mhada_gemm_tn(const mhada_gemm_tn_args* a, float* work, long long
   }
   if (p.nb > 1) return fail("mhada_gemm_tn: batched column sums need 16-B aligned A with M % 4 == 0");
   // unfused: the column sums of A [K][lda] over its first M columns (the workspace is free again)
-  if (a->lda != p.M || p.M % 4 || !al16(a->a)) return fail("mhada_gemm_tn: colsum needs a dense, aligned A");
+  if (a->lda != p.M || p.M % 4 || !aligned16(a->a)) return fail("mhada_gemm_tn: colsum needs a dense, aligned A");
   return mhada_colsum(a->a, a->colsum, p.K, p.M, work, work_floats, s_);
 }
 
 extern "C" int mhada_colsum(const float* x, float* out, long long rows, int C, float* work, long long work_floats,
                             mhada_stream_t s_) {
   if (!x || !out || !work || rows <= 0 || C <= 0) return fail("mhada_colsum: bad args");
-  if (C % 4 || !al16(x) || !al16(work)) return fail("mhada_colsum: C % 4 == 0 and 16-byte aligned x, work");
+  if (C % 4 || !aligned16(x) || !aligned16(work)) return fail("mhada_colsum: C % 4 == 0 and 16-byte aligned x, work");
   // up to 128 blocks of at least 64 rows (the fixed-order reduction pass loops over the chunks)
   long long chunks = std::min<long long>(std::max<long long>(1, rows / 64), 128);
   chunks = std::min<long long>(chunks, work_floats / C);
@@ -1291,7 +1279,7 @@ extern "C" int mhada_colsum(const float* x, float* out, long long rows, int C, f
 static int layernorm_fwd_launch(const float* x, float* y, void* planes, float* stats, const float* gamma,
                                 const float* beta, int rows, int cols, float eps, hipStream_t s) {
   if (!x || !y || !stats || !gamma || !beta || rows <= 0) return fail("mhada_layernorm_fwd: bad args");
-  if (!al16(x) || !al16(y) || !al16(gamma) || !al16(beta) || ((uintptr_t)stats & 7) || ((uintptr_t)planes & 7))
+  if (!aligned16(x) || !aligned16(y) || !aligned16(gamma) || !aligned16(beta) || ((uintptr_t)stats & 7) || ((uintptr_t)planes & 7))
     return fail("mhada_layernorm_fwd: x, y, gamma, beta 16-byte aligned, stats and planes 8-byte aligned");
   const dim3 grid((unsigned)((rows + 3) / 4));
   bf16* pl = reinterpret_cast<bf16*>(planes);
@@ -1320,7 +1308,7 @@ extern "C" int mhada_layernorm_bwd(const float* x, const float* dy, const float*
                                    mhada_stream_t s_) {
   if (!x || !dy || !stats || !gamma || !dx || !dgamma || !dbeta || !work || rows <= 0)
     return fail("mhada_layernorm_bwd: bad args");
-  if (!al16(x) || !al16(dy) || !al16(gamma) || !al16(dx) || !al16(work) || ((uintptr_t)stats & 7))
+  if (!aligned16(x) || !aligned16(dy) || !aligned16(gamma) || !aligned16(dx) || !aligned16(work) || ((uintptr_t)stats & 7))
     return fail("mhada_layernorm_bwd: 16-byte aligned operands");
   const int nblk = (rows + kLnBwdRows - 1) / kLnBwdRows;
   if (work_floats < (long long)nblk * 2 * cols + 2LL * cols) return fail("mhada_layernorm_bwd: workspace too small");
@@ -1346,7 +1334,7 @@ extern "C" int mhada_instnorm_bwd(const float* dy, const float* y, const float* 
                                   int B, int N, int C, int splits, mhada_stream_t s_) {
   if (!dy || !y || !rstd || !dx || !work || B <= 0 || N <= 0 || C <= 0 || splits <= 0 || splits > 65535)
     return fail("mhada_instnorm_bwd: bad args");
-  if (C % 4 || !al16(dy) || !al16(y) || !al16(rstd) || !al16(dx) || !al16(work))
+  if (C % 4 || !aligned16(dy) || !aligned16(y) || !aligned16(rstd) || !aligned16(dx) || !aligned16(work))
     return fail("mhada_instnorm_bwd: C % 4 == 0 and 16-byte aligned operands");
   hipStream_t s = (hipStream_t)s_;
   hipLaunchKernelGGL(inb_partial_kernel, dim3((C + 63) / 64, B, splits), dim3(256), 0, s, dy, y, work, B, N, C, splits);
@@ -1395,7 +1383,7 @@ extern "C" int mhada_pos_embed_bwd(const float* g, float* gpos, int C, int bh, i
 }
 
 extern "C" int mhada_relu_bwd(const float* dy, const float* y, float* dx, long long n, mhada_stream_t s_) {
-  if (!dy || !y || !dx || n <= 0 || n % 4 || !al16(dy) || !al16(y) || !al16(dx))
+  if (!dy || !y || !dx || n <= 0 || n % 4 || !aligned16(dy) || !aligned16(y) || !aligned16(dx))
     return fail("mhada_relu_bwd: bad args (n % 4 == 0, 16-byte aligned)");
   hipLaunchKernelGGL(relu_bwd_kernel, grid1(n / 4), dim3(256), 0, (hipStream_t)s_, dy, y, dx, n / 4);
   return check_launch("mhada_relu_bwd");
@@ -1523,7 +1511,7 @@ __global__ void __launch_bounds__(256) feat_stats_finalize_kernel(const double* 
 extern "C" int mhada_feat_stats(const float* x, const float* t, float* mu, float* sd, float* mse, double* work,
                                 long long work_doubles, int B, long long P, int C, mhada_stream_t s_) {
   const bool stats = mu && sd;
-  if (!x || B <= 0 || P <= 0 || C <= 0 || C % 4 || !al16(x) || (t && !al16(t)) || (!stats && !(t && mse)) ||
+  if (!x || B <= 0 || P <= 0 || C <= 0 || C % 4 || !aligned16(x) || (t && !aligned16(t)) || (!stats && !(t && mse)) ||
       (bool)t != (bool)mse || !work)
     return fail("mhada_feat_stats: bad args (C % 4 == 0, 16-byte aligned; mean + std and / or t + mse)");
   const int cb = (C + 63) / 64;
@@ -1554,9 +1542,9 @@ extern "C" long long mhada_feat_stats_work(int B, long long P, int C) {
 extern "C" int mhada_feat_loss_bwd(const float* x, const float* t, const float* mu, const float* alpha,
                                    const float* beta, const float* kp, float ks, float* g, int B, long long P,
                                    int C, int relu, mhada_stream_t s_) {
-  if (!x || !g || B <= 0 || P <= 0 || C <= 0 || C % 4 || !al16(x) || !al16(g) || (t && !al16(t)))
+  if (!x || !g || B <= 0 || P <= 0 || C <= 0 || C % 4 || !aligned16(x) || !aligned16(g) || (t && !aligned16(t)))
     return fail("mhada_feat_loss_bwd: bad args (C % 4 == 0, 16-byte aligned)");
-  if (alpha && (!beta || !mu || !al16(alpha) || !al16(beta) || !al16(mu)))
+  if (alpha && (!beta || !mu || !aligned16(alpha) || !aligned16(beta) || !aligned16(mu)))
     return fail("mhada_feat_loss_bwd: alpha needs beta and mu (16-byte aligned)");
   const long long n4 = (long long)B * P * (C / 4);
   hipLaunchKernelGGL(feat_loss_bwd_kernel, grid1(n4), dim3(256), 0, (hipStream_t)s_, x, t, mu, alpha, beta, kp, ks,
@@ -1566,7 +1554,7 @@ extern "C" int mhada_feat_loss_bwd(const float* x, const float* t, const float* 
 
 extern "C" int mhada_reflect_fold(const float* dxp, float* dx, int B, int H, int W, int C, const float* relu_mask,
                                   mhada_stream_t s_) {
-  if (!dxp || !dx || B <= 0 || H < 2 || W < 2 || C % 4 || !al16(dxp) || !al16(dx) || (relu_mask && !al16(relu_mask)))
+  if (!dxp || !dx || B <= 0 || H < 2 || W < 2 || C % 4 || !aligned16(dxp) || !aligned16(dx) || (relu_mask && !aligned16(relu_mask)))
     return fail("mhada_reflect_fold: bad args");
   hipLaunchKernelGGL(reflect_fold_kernel, grid1((long long)B * H * W * (C / 4)), dim3(256), 0, (hipStream_t)s_, dxp, dx,
                      B, H, W, C, relu_mask);
@@ -1574,7 +1562,7 @@ extern "C" int mhada_reflect_fold(const float* dxp, float* dx, int B, int H, int
 }
 
 extern "C" int mhada_maxpool2(const float* x, float* y, int B, int H, int W, int C, mhada_stream_t s_) {
-  if (!x || !y || B <= 0 || H < 2 || W < 2 || C % 4 || !al16(x) || !al16(y)) return fail("mhada_maxpool2: bad args");
+  if (!x || !y || B <= 0 || H < 2 || W < 2 || C % 4 || !aligned16(x) || !aligned16(y)) return fail("mhada_maxpool2: bad args");
   hipLaunchKernelGGL(maxpool2_kernel, grid1((long long)B * (H / 2) * (W / 2) * (C / 4)), dim3(256), 0, (hipStream_t)s_,
                      x, y, B, H, W, C);
   return check_launch("mhada_maxpool2");
@@ -1582,7 +1570,7 @@ extern "C" int mhada_maxpool2(const float* x, float* y, int B, int H, int W, int
 
 extern "C" int mhada_maxpool2_bwd(const float* x, const float* dy, float* dx, int B, int H, int W, int C,
                                   int relu_mask, mhada_stream_t s_) {
-  if (!x || !dy || !dx || B <= 0 || H < 2 || W < 2 || C % 4 || !al16(x) || !al16(dy) || !al16(dx))
+  if (!x || !dy || !dx || B <= 0 || H < 2 || W < 2 || C % 4 || !aligned16(x) || !aligned16(dy) || !aligned16(dx))
     return fail("mhada_maxpool2_bwd: bad args");
   if (H % 2 || W % 2) (void)hipMemsetAsync(dx, 0, (size_t)B * H * W * C * sizeof(float), (hipStream_t)s_);
   hipLaunchKernelGGL(maxpool2_bwd_kernel, grid1((long long)B * (H / 2) * (W / 2) * (C / 4)), dim3(256), 0,
@@ -1592,7 +1580,7 @@ extern "C" int mhada_maxpool2_bwd(const float* x, const float* dy, float* dx, in
 
 extern "C" int mhada_upsample2x_bwd(const float* dy, const float* relu_x, float* dx, int B, int H, int W, int C,
                                     mhada_stream_t s_) {
-  if (!dy || !dx || B <= 0 || H <= 0 || W <= 0 || C % 4 || !al16(dy) || !al16(dx) || !al16(relu_x))
+  if (!dy || !dx || B <= 0 || H <= 0 || W <= 0 || C % 4 || !aligned16(dy) || !aligned16(dx) || !aligned16(relu_x))
     return fail("mhada_upsample2x_bwd: bad args");
   hipLaunchKernelGGL(upsample2x_bwd_kernel, grid1((long long)B * H * W * (C / 4)), dim3(256), 0, (hipStream_t)s_, dy,
                      relu_x, dx, B, H, W, C);

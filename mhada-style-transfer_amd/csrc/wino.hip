@@ -74,10 +74,6 @@ struct WinoP {
   int nbx, nby, nbn, nblk;
 };
 
-MHADA_DEV int reflect_clamp(int v, int n) {
-  v = v < 0 ? -v : (v >= n ? 2 * n - 2 - v : v);
-  return min(max(v, 0), n - 1);
-}
 // float offset of the 16-B half `half` (channels 4*half .. 4*half+3) of 32-B row `row`: halves
 // swapped on rows with bit 3 set, so ds_read_b128 of 32 consecutive rows is conflict-free
 MHADA_DEV int swz(int row, int half) { return row * 8 + ((half ^ ((row >> 3) & 1)) << 2); }
@@ -89,11 +85,55 @@ MHADA_DEV int rswz(int slot) { return slot ^ (((slot >> 3) & 1) << 1); }
 // tile row per half-wave (pixels 2 apart = 4 slots): bit 1 of the slot flips with bit 4, so tiles
 // t and t + 4 (16 slots apart) land on different 16-B bank groups.
 MHADA_DEV int rswz4(int slot) { return slot ^ (((slot >> 4) & 1) << 1); }
-MHADA_DEV void glds16(const float* src, float* lds) {  // LDS-DMA: lane l -> lds + 16 l bytes
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                   (__attribute__((address_space(3))) void*)lds, 16, 0, 0);
+
+// The workgroup's logical block: output-channel block nb, tile block (by, bx) of image b.
+struct WinoBlock { int nb, bx, by, b; };
+// output-channel block fastest (neighbours share the input patch in L2): wino_kernel, wino4_kernel
+MHADA_DEV WinoBlock wino_block_co_inner(const WinoP& p) {
+  WinoBlock k;
+  int id = xcd_remap(blockIdx.x, p.nblk);
+  k.nb = id % p.nbn;
+  id /= p.nbn;
+  k.bx = id % p.nbx;
+  id /= p.nbx;
+  k.by = id % p.nby;
+  k.b = id / p.nby;
+  return k;
+}
+// output-channel block outermost (an XCD's contiguous id range shares a U slice): the SPLIT3 kernels
+MHADA_DEV WinoBlock wino_block_co_outer(const WinoP& p) {
+  WinoBlock k;
+  int id = xcd_remap(blockIdx.x, p.nblk);
+  const int nsp = p.nblk / p.nbn;
+  k.nb = id / nsp;
+  id -= k.nb * nsp;
+  k.bx = id % p.nbx;
+  id /= p.nbx;
+  k.by = id % p.nby;
+  k.b = id / p.nby;
+  return k;
 }
 
+// Epilogue of one output column: s0 / s1 = the output transform's finished sums for rows oy0, oy0 + 1 of
+// column ox, channel co of image b; adds the bias, then ReLU, the ReLU-adjoint mask and the bounds.
+MHADA_DEV void wino_store(const WinoP& p, float s0, float s1, float bias, int b, int oy0, int ox, int co) {
+  float y0 = s0 + bias;
+  float y1 = s1 + bias;
+  if (p.relu) {
+    y0 = fmaxf(y0, 0.f);
+    y1 = fmaxf(y1, 0.f);
+  }
+  if (ox < p.Wo) {
+    const long long i0 = ((long long)(b * p.Ho + oy0) * p.Wo + ox) * p.ldc + co;
+    const long long i1 = i0 + (long long)p.Wo * p.ldc;
+    if (p.mask) {
+      if (oy0 < p.Ho && !(p.mask[i0] > 0.f)) y0 = 0.f;
+      if (oy0 + 1 < p.Ho && !(p.mask[i1] > 0.f)) y1 = 0.f;
+    }
+    if (oy0 < p.Ho) p.y[i0] = y0;
+    if (oy0 + 1 < p.Ho) p.y[i1] = y1;
+  }
+}
 
 __global__ void __launch_bounds__(512, 1) wino_kernel(const WinoP p) {
   __shared__ __attribute__((aligned(16))) float lds[2 * (kVS + kUS + kRS)];  // 150 KiB
@@ -107,15 +147,9 @@ __global__ void __launch_bounds__(512, 1) wino_kernel(const WinoP p) {
   // and every wave issues a share of the LDS-DMA
   const int e = wave >> 2, th = wave & 1, ch = (wave >> 1) & 1;
 
-  // logical block: output-channel block fastest (neighbours share the input patch in L2)
-  int id = xcd_remap(blockIdx.x, p.nblk);
-  const int nb = id % p.nbn;
-  id /= p.nbn;
-  const int bx = id % p.nbx;
-  id /= p.nbx;
-  const int by = id % p.nby;
-  const int b = id / p.nby;
-  const int co0 = nb * kCO;
+  const WinoBlock blk = wino_block_co_inner(p);
+  const int bx = blk.bx, by = blk.by, b = blk.b;
+  const int co0 = blk.nb * kCO;
   const int P = p.zero ? p.pad : 1;
   const int nck = p.Cin / kCK;
 
@@ -278,7 +312,7 @@ __global__ void __launch_bounds__(512, 1) wino_kernel(const WinoP p) {
   const float bias = p.bias ? p.bias[co] : 0.f;
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    const int tile = 32 * th + (r & 3) + 8 * (r >> 2) + 4 * h;
+    const int tile = 32 * th + acc_row(r, h);
     float m[2][2];
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
@@ -288,25 +322,9 @@ __global__ void __launch_bounds__(512, 1) wino_kernel(const WinoP p) {
     }
     const int oy0 = 2 * (by * kT + (tile >> 3)), ox0 = 2 * (bx * kT + (tile & 7));
 #pragma unroll
-    for (int q = 0; q < 2; ++q) {
-      float y0 = m[0][q] + m[1][q] + ex[(r * 4 + 2 * q) * 64] + bias;
-      float y1 = m[1][q] + ex[(r * 4 + 2 * q + 1) * 64] + bias;
-      if (p.relu) {
-        y0 = fmaxf(y0, 0.f);
-        y1 = fmaxf(y1, 0.f);
-      }
-      const int ox = ox0 + q;
-      if (ox < p.Wo) {
-        const long long i0 = ((long long)(b * p.Ho + oy0) * p.Wo + ox) * p.ldc + co;
-        const long long i1 = i0 + (long long)p.Wo * p.ldc;
-        if (p.mask) {
-          if (oy0 < p.Ho && !(p.mask[i0] > 0.f)) y0 = 0.f;
-          if (oy0 + 1 < p.Ho && !(p.mask[i1] > 0.f)) y1 = 0.f;
-        }
-        if (oy0 < p.Ho) p.y[i0] = y0;
-        if (oy0 + 1 < p.Ho) p.y[i1] = y1;
-      }
-    }
+    for (int q = 0; q < 2; ++q)
+      wino_store(p, m[0][q] + m[1][q] + ex[(r * 4 + 2 * q) * 64], m[1][q] + ex[(r * 4 + 2 * q + 1) * 64], bias, b, oy0,
+                 ox0 + q, co);
   }
 }
 
@@ -336,14 +354,9 @@ __global__ void __launch_bounds__(256, 1) wino4_kernel(const WinoP p) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int th = wave & 1, ch = wave >> 1;
 
-  int id = xcd_remap(blockIdx.x, p.nblk);
-  const int nb = id % p.nbn;
-  id /= p.nbn;
-  const int bx = id % p.nbx;
-  id /= p.nbx;
-  const int by = id % p.nby;
-  const int b = id / p.nby;
-  const int co0 = nb * kCO;
+  const WinoBlock blk = wino_block_co_inner(p);
+  const int bx = blk.bx, by = blk.by, b = blk.b;
+  const int co0 = blk.nb * kCO;
   const int P = p.zero ? p.pad : 1;
   const int nck = p.Cin / kCK;
 
@@ -498,7 +511,7 @@ __global__ void __launch_bounds__(256, 1) wino4_kernel(const WinoP p) {
   const float bias = p.bias ? p.bias[co] : 0.f;
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    const int tile = 32 * th + (r & 3) + 8 * (r >> 2) + 4 * h;
+    const int tile = 32 * th + acc_row(r, h);
     float m[4][2];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -510,23 +523,7 @@ __global__ void __launch_bounds__(256, 1) wino4_kernel(const WinoP p) {
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
       const float e1 = -m[2][q] - m[3][q];
-      float y0 = m[0][q] + m[1][q] + m[2][q] + bias;
-      float y1 = m[1][q] + e1 + bias;
-      if (p.relu) {
-        y0 = fmaxf(y0, 0.f);
-        y1 = fmaxf(y1, 0.f);
-      }
-      const int ox = ox0 + q;
-      if (ox < p.Wo) {
-        const long long i0 = ((long long)(b * p.Ho + oy0) * p.Wo + ox) * p.ldc + co;
-        const long long i1 = i0 + (long long)p.Wo * p.ldc;
-        if (p.mask) {
-          if (oy0 < p.Ho && !(p.mask[i0] > 0.f)) y0 = 0.f;
-          if (oy0 + 1 < p.Ho && !(p.mask[i1] > 0.f)) y1 = 0.f;
-        }
-        if (oy0 < p.Ho) p.y[i0] = y0;
-        if (oy0 + 1 < p.Ho) p.y[i1] = y1;
-      }
+      wino_store(p, m[0][q] + m[1][q] + m[2][q], m[1][q] + e1, bias, b, oy0, ox0 + q, co);
     }
   }
 }
@@ -568,6 +565,32 @@ struct WinoS3P : WinoP {
 // tiles of a tile row) cover all four 64-B quarters of the 256-B bank row
 MHADA_DEV int rpix(int pix) { return pix ^ ((pix >> 2) & 1); }
 
+// Byte offset in x of the 16 B that the SPLIT3 kernels' raw-patch DMA puts into LDS slot `slot` = pixel
+// position (slot >> 2), channel quad (slot & 3) of tile block (by, bx) of image b; 0x7ff00000 (past the
+// buffer) reads zero padding
+MHADA_DEV int s3_raw_offset(const WinoP& p, int slot, int b, int by, int bx, int P) {
+  const int pix = rpix(slot >> 2);
+  int iy = 2 * by * kT - P + pix / kRP, ix = 2 * bx * kT - P + pix % kRP;
+  bool inside = pix < kRaw;
+  if (p.zero) {
+    inside = inside && iy >= 0 && iy < p.H && ix >= 0 && ix < p.W;
+  } else {
+    iy = reflect_clamp(iy, p.H);
+    ix = reflect_clamp(ix, p.W);
+  }
+  return inside ? (((b * p.H + iy) * p.W + ix) * p.Cin + 4 * (slot & 3)) * 4 : 0x7ff00000;
+}
+
+// the three bf16 planes of v into the V image: plane pl at dst + pl * kSImg bytes
+MHADA_DEV void s3_split_store(const f32x4 v, unsigned char* dst) {
+  bf16x4 p0, p1, p2;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) split3_into(v[e], p0, p1, p2, e);
+  *reinterpret_cast<bf16x4*>(dst) = p0;
+  *reinterpret_cast<bf16x4*>(dst + kSImg) = p1;
+  *reinterpret_cast<bf16x4*>(dst + 2 * kSImg) = p2;
+}
+
 __global__ void __launch_bounds__(256, 1) wino_s3_kernel(const WinoS3P p) {
   __shared__ __attribute__((aligned(16))) unsigned char sV0[kSStage];
   __shared__ __attribute__((aligned(16))) unsigned char sV1[kSStage];
@@ -579,16 +602,9 @@ __global__ void __launch_bounds__(256, 1) wino_s3_kernel(const WinoS3P p) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int th = wave & 1, ch = wave >> 1;
 
-  // logical block: output-channel block outermost (an XCD's contiguous id range shares a U slice)
-  int id = xcd_remap(blockIdx.x, p.nblk);
-  const int nsp = p.nblk / p.nbn;
-  const int nb = id / nsp;
-  id -= nb * nsp;
-  const int bx = id % p.nbx;
-  id /= p.nbx;
-  const int by = id % p.nby;
-  const int b = id / p.nby;
-  const int co0 = nb * kCO;
+  const WinoBlock blk = wino_block_co_outer(p);
+  const int bx = blk.bx, by = blk.by, b = blk.b;
+  const int co0 = blk.nb * kCO;
   const int P = p.zero ? p.pad : 1;
   const int nck = p.Cin / kSK, nst = 4 * nck;
 
@@ -597,23 +613,10 @@ __global__ void __launch_bounds__(256, 1) wino_s3_kernel(const WinoS3P p) {
       const_cast<float*>(p.x), 0, (int)((long long)p.B * p.H * p.W * p.Cin * 4), 0x00020000);
   const __amdgpu_buffer_rsrc_t ur =
       __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16*>(p.up), 0, p.Cin * p.Cout * 96, 0x00020000);
-  // raw patch DMA: instruction j = wave + 4 t (j < 21) fills 16-B slots 64 j + lane = pixel
-  // position (slot >> 2), channel quad (slot & 3); 0x7ff00000 (past the buffer) reads zero padding
+  // raw patch DMA: instruction j = wave + 4 t (j < 21) fills 16-B slots 64 j + lane
   int rvo[6];
 #pragma unroll
-  for (int t = 0; t < 6; ++t) {
-    const int slot = 64 * (wave + 4 * t) + lane;
-    const int pix = rpix(slot >> 2);
-    int iy = 2 * by * kT - P + pix / kRP, ix = 2 * bx * kT - P + pix % kRP;
-    bool inside = pix < kRaw;
-    if (p.zero) {
-      inside = inside && iy >= 0 && iy < p.H && ix >= 0 && ix < p.W;
-    } else {
-      iy = reflect_clamp(iy, p.H);
-      ix = reflect_clamp(ix, p.W);
-    }
-    rvo[t] = inside ? (((b * p.H + iy) * p.W + ix) * p.Cin + 4 * (slot & 3)) * 4 : 0x7ff00000;
-  }
+  for (int t = 0; t < 6; ++t) rvo[t] = s3_raw_offset(p, 64 * (wave + 4 * t) + lane, b, by, bx, P);
   // U DMA: instructions 6w .. 6w+5 of 24; slot 64 j + lane = (xi * 3 + plane, co row, stored half),
   // the source half is the logical one (swz); byte offsets inside one stage
   int uvo[6];
@@ -648,21 +651,7 @@ __global__ void __launch_bounds__(256, 1) wino_s3_kernel(const WinoS3P p) {
     }
     const f32x4 v[4] = {t[0] - t[2], t[1] + t[2], t[2] - t[1], t[1] - t[3]};
 #pragma unroll
-    for (int x = 0; x < 4; ++x) {
-      bf16x4 p0, p1, p2;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const bf16 a = (bf16)v[x][e];
-        const float r = v[x][e] - (float)a;
-        const bf16 c = (bf16)r;
-        p0[e] = a;
-        p1[e] = c;
-        p2[e] = (bf16)(r - (float)c);
-      }
-      *reinterpret_cast<bf16x4*>(sv + (3 * x + 0) * kSImg + vdst) = p0;
-      *reinterpret_cast<bf16x4*>(sv + (3 * x + 1) * kSImg + vdst) = p1;
-      *reinterpret_cast<bf16x4*>(sv + (3 * x + 2) * kSImg + vdst) = p2;
-    }
+    for (int x = 0; x < 4; ++x) s3_split_store(v[x], sv + 3 * x * kSImg + vdst);
   };
 
   f32x16 acc[16];
@@ -753,7 +742,7 @@ __global__ void __launch_bounds__(256, 1) wino_s3_kernel(const WinoS3P p) {
   const float bias = p.bias ? p.bias[co] : 0.f;
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    const int tile = 32 * th + (r & 3) + 8 * (r >> 2) + 4 * h;
+    const int tile = 32 * th + acc_row(r, h);
     float m[4][2];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -765,23 +754,7 @@ __global__ void __launch_bounds__(256, 1) wino_s3_kernel(const WinoS3P p) {
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
       const float e1 = -m[2][q] - m[3][q];
-      float y0 = m[0][q] + m[1][q] + m[2][q] + bias;
-      float y1 = m[1][q] + e1 + bias;
-      if (p.relu) {
-        y0 = fmaxf(y0, 0.f);
-        y1 = fmaxf(y1, 0.f);
-      }
-      const int ox = ox0 + q;
-      if (ox < p.Wo) {
-        const long long i0 = ((long long)(b * p.Ho + oy0) * p.Wo + ox) * p.ldc + co;
-        const long long i1 = i0 + (long long)p.Wo * p.ldc;
-        if (p.mask) {
-          if (oy0 < p.Ho && !(p.mask[i0] > 0.f)) y0 = 0.f;
-          if (oy0 + 1 < p.Ho && !(p.mask[i1] > 0.f)) y1 = 0.f;
-        }
-        if (oy0 < p.Ho) p.y[i0] = y0;
-        if (oy0 + 1 < p.Ho) p.y[i1] = y1;
-      }
+      wino_store(p, m[0][q] + m[1][q] + m[2][q], m[1][q] + e1, bias, b, oy0, ox0 + q, co);
     }
   }
 }
@@ -817,16 +790,9 @@ __global__ void __launch_bounds__(256, 1) wino_s3_rows_kernel(const WinoS3P p) {
   const int tid = threadIdx.x, lane = tid & 63, h = lane >> 5, r32 = lane & 31;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
 
-  // logical block: wino_s3_kernel's order
-  int id = xcd_remap(blockIdx.x, p.nblk);
-  const int nsp = p.nblk / p.nbn;
-  const int nb = id / nsp;
-  id -= nb * nsp;
-  const int bx = id % p.nbx;
-  id /= p.nbx;
-  const int by = id % p.nby;
-  const int b = id / p.nby;
-  const int co0 = nb * kCO;
+  const WinoBlock blk = wino_block_co_outer(p);
+  const int bx = blk.bx, by = blk.by, b = blk.b;
+  const int co0 = blk.nb * kCO;
   const int P = p.zero ? p.pad : 1;
   const int nck = p.Cin / kSK;
 
@@ -837,19 +803,7 @@ __global__ void __launch_bounds__(256, 1) wino_s3_rows_kernel(const WinoS3P p) {
   // raw patch DMA: wino_s3_kernel's slots
   int rvo[6];
 #pragma unroll
-  for (int t = 0; t < 6; ++t) {
-    const int slot = 64 * (wave + 4 * t) + lane;
-    const int pix = rpix(slot >> 2);
-    int iy = 2 * by * kT - P + pix / kRP, ix = 2 * bx * kT - P + pix % kRP;
-    bool inside = pix < kRaw;
-    if (p.zero) {
-      inside = inside && iy >= 0 && iy < p.H && ix >= 0 && ix < p.W;
-    } else {
-      iy = reflect_clamp(iy, p.H);
-      ix = reflect_clamp(ix, p.W);
-    }
-    rvo[t] = inside ? (((b * p.H + iy) * p.W + ix) * p.Cin + 4 * (slot & 3)) * 4 : 0x7ff00000;
-  }
+  for (int t = 0; t < 6; ++t) rvo[t] = s3_raw_offset(p, 64 * (wave + 4 * t) + lane, b, by, bx, P);
   typedef __attribute__((address_space(3))) void* LdsP;
   auto dma_raw = [&](int k, unsigned char* sr) {
     const int so = min(k, nck - 1) * kSK * 4;
@@ -885,19 +839,7 @@ __global__ void __launch_bounds__(256, 1) wino_s3_rows_kernel(const WinoS3P p) {
   }
   const int vdst = tl * 32 + ((((tq >> 1) ^ (tl >> 3)) & 1) << 4) + (tq & 1) * 8;
   auto split_store = [&](const f32x4 v, int x, int it) {  // the three planes of position x of item it
-    bf16x4 p0, p1, p2;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const bf16 a = (bf16)v[e];
-      const float r = v[e] - (float)a;
-      const bf16 c = (bf16)r;
-      p0[e] = a;
-      p1[e] = c;
-      p2[e] = (bf16)(r - (float)c);
-    }
-    *reinterpret_cast<bf16x4*>(sv + (3 * x + 0) * kSImg + it * 512 + vdst) = p0;
-    *reinterpret_cast<bf16x4*>(sv + (3 * x + 1) * kSImg + it * 512 + vdst) = p1;
-    *reinterpret_cast<bf16x4*>(sv + (3 * x + 2) * kSImg + it * 512 + vdst) = p2;
+    s3_split_store(v, sv + 3 * x * kSImg + it * 512 + vdst);
   };
   f32x4 hold[4][2];  // positions 2, 3 of the next chunk's items until their V space is free
   auto transform_a = [&](const unsigned char* sr) {
@@ -1009,7 +951,7 @@ __global__ void __launch_bounds__(256, 1) wino_s3_rows_kernel(const WinoS3P p) {
       for (int cb = 0; cb < 2; ++cb)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int tile = 32 * tb + (r & 3) + 8 * (r >> 2) + 4 * h;
+          const int tile = 32 * tb + acc_row(r, h);
           const float m0 = acc[2 * tb + cb][r], m1 = acc[4 + 2 * tb + cb][r], m2 = acc[8 + 2 * tb + cb][r],
                       m3 = acc[12 + 2 * tb + cb][r];
           ex[(wave * kTT + tile) * kCO + 32 * cb + r32] = q ? m1 - m2 - m3 : m0 + m1 + m2;
@@ -1023,22 +965,7 @@ __global__ void __launch_bounds__(256, 1) wino_s3_rows_kernel(const WinoS3P p) {
       for (int i = 0; i < 4; ++i) m[i] = ex[(i * kTT + tile) * kCO + lane];
       const int oy0 = 2 * (by * kT + (tile >> 3)), ox = 2 * (bx * kT + (tile & 7)) + q;
       const float e1 = -m[2] - m[3];
-      float y0 = m[0] + m[1] + m[2] + bias;
-      float y1 = m[1] + e1 + bias;
-      if (p.relu) {
-        y0 = fmaxf(y0, 0.f);
-        y1 = fmaxf(y1, 0.f);
-      }
-      if (ox < p.Wo) {
-        const long long i0 = ((long long)(b * p.Ho + oy0) * p.Wo + ox) * p.ldc + co;
-        const long long i1 = i0 + (long long)p.Wo * p.ldc;
-        if (p.mask) {
-          if (oy0 < p.Ho && !(p.mask[i0] > 0.f)) y0 = 0.f;
-          if (oy0 + 1 < p.Ho && !(p.mask[i1] > 0.f)) y1 = 0.f;
-        }
-        if (oy0 < p.Ho) p.y[i0] = y0;
-        if (oy0 + 1 < p.Ho) p.y[i1] = y1;
-      }
+      wino_store(p, m[0] + m[1] + m[2], m[1] + e1, bias, b, oy0, ox, co);
     }
   }
 }
@@ -1068,13 +995,11 @@ __global__ void wino_weights_s3_kernel(const float* __restrict__ w, bf16* __rest
     const float v[4] = {a, 0.5f * (a + bb + c), 0.5f * (a - bb + c), c};
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      const bf16 p0 = (bf16)v[j];
-      const float r1 = v[j] - (float)p0;
-      const bf16 p1 = (bf16)r1;
+      const Bf3 s = split3(v[j]);
       bf16* o = ub + (long long)(4 * r + j) * 3 * Cout * kSK;
-      o[0] = p0;
-      o[(long long)Cout * kSK] = p1;
-      o[2LL * Cout * kSK] = (bf16)(r1 - (float)p1);
+      o[0] = s.a;
+      o[(long long)Cout * kSK] = s.b;
+      o[2LL * Cout * kSK] = s.c;
     }
   }
 }
@@ -1357,7 +1282,7 @@ __global__ void __launch_bounds__(512, 1) wino_wgrad_kernel(const WgP p) {
   for (int x = 0; x < 8; ++x)
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int co = co0 + 32 * coh + (r & 3) + 8 * (r >> 2) + 4 * h, ci = ci0 + 32 * cih + r32;
+      const int co = co0 + 32 * coh + acc_row(r, h), ci = ci0 + 32 * cih + r32;
       sl[((long long)(8 * e + x) * p.Cout + co) * p.Cin + ci] = acc[x][r];
     }
   if (p.cslab && ib == 0) {  // the 8 tile lanes of a co are consecutive lanes: fixed-order xor tree
