@@ -522,6 +522,58 @@ int mhada_flow_warp_mask(const float* flo01, const float* flo10, float* mask, in
 int mhada_warp_l1(const float* cs1, const float* cs2, const float* flow, const float* mask,
                   double* work, float* out, int B, int C, int H, int W, mhada_stream_t stream);
 
+/* ---- temporal losses of train_video.py (additive to ABI 18; csrc/temporal.hip) ------------------
+ *
+ * Added to ABI 18 WITHOUT a version bump, for the reasons given for the _hd entries above: the
+ * three entries are purely additive and are found by symbol.
+ *
+ * No entry synchronises with the host: the reference's torch.nonzero(m).shape[0] (lossfn.py:66,86,
+ * a device-to-host copy) becomes a count reduced on the device.  The one departure: an all-zero
+ * mask gives NaN (0 / 0) where the reference raises ZeroDivisionError. */
+
+/* Workgroups of the forward's partial reduction, and the workspace in 8-byte words: word 0 the
+ * count of m != 0 (int64, what the backward reads), then the workgroups' fp64 partial sums and
+ * their int64 counts.  The workspace must be 8-byte aligned; the forward writes every word it
+ * later reads. */
+#define MHADA_TEMPORAL_MAX_BLOCKS 2048
+#define MHADA_TEMPORAL_WORK_WORDS (1 + 2 * MHADA_TEMPORAL_MAX_BLOCKS)
+
+/* One masked, warped MSE (lossfn.py:50-66 output level with c1 / c2, lossfn.py:81-86 feature level
+ * without):
+ *   out[0] = sum_{b,c,y,x} m[b,y,x] * (x2 - warp(x1, flow) - t[b,y,x])^2 / (C * #{m != 0})
+ * x1, x2: fp32 [B][C][H][W] with the element strides sx1 / sx2 = {b, c, y, x} (HOST arrays of four,
+ * read before the launch; non-negative): contiguous NCHW and channels_last views both run without
+ * a copy, the thread mapping follows the channel stride.  flow [B][2][H][W], m [B][H][W]
+ * contiguous.  c1, c2: both NULL (t = 0), or contiguous [B][3][H][W]: t = 0.2126 r + 0.7152 g +
+ * 0.0722 b of c2 - warp(c1, flow) (lossfn.py:52-53), in the reference's operation order.  The warp
+ * is mhada_warp's (zero padding).  m weighs each term as a float; the count is of its nonzero
+ * entries.  fp64 partial sums per workgroup and a fixed-order finalize: out (a device fp32 scalar)
+ * is bit-identical from run to run.  work: MHADA_TEMPORAL_WORK_WORDS words. */
+int mhada_temporal_loss_fwd(const float* x1, const long long* sx1, const float* x2,
+                            const long long* sx2, const float* flow, const float* m,
+                            const float* c1, const float* c2, void* work, float* out, int B, int C,
+                            int H, int W, mhada_stream_t stream);
+
+/* Its backward (autograd of lossfn.py:50-66 / 81-86 w.r.t. cs1, cs2 / f1, f2) for the upstream
+ * gradient gout (a DEVICE fp32 scalar) and the count the forward left in work:
+ *   r = 2 m (x2 - warp(x1, flow) - t) gout / (C count);  dx2 = r;  dx1[taps] -= w_tap r
+ * dx2 is written in full with its own strides sdx2 (deterministic).  dx1 must be zeroed by the
+ * caller and is scattered to with fp32 atomics as mhada_warp_bwd does (zero r skipped; the
+ * summation order at a tap hit by several pixels is not fixed, as in ATen).  Either of dx1 / dx2
+ * may be NULL.  c1, c2, flow and m take no gradient. */
+int mhada_temporal_loss_bwd(const float* x1, const long long* sx1, const float* x2,
+                            const long long* sx2, const float* flow, const float* m,
+                            const float* c1, const float* c2, const void* work, const float* gout,
+                            float* dx1, const long long* sdx1, float* dx2, const long long* sdx2,
+                            int B, int C, int H, int W, mhada_stream_t stream);
+
+/* The feature-level prologue (lossfn.py:71-80) in one launch: fflow [B][2][Hf][Wf] =
+ * F.interpolate(flow, (Hf, Wf), mode="bilinear") (align_corners=False, no antialias, the source
+ * index clamped at 0) with channel 0 scaled by Wf / W and channel 1 by Hf / H; fmask [B][Hf][Wf] =
+ * (the same resize of mask [B][H][W]) > 0 as 0 / 1 floats. */
+int mhada_flow_mask_resize(const float* flow, const float* mask, float* fflow, float* fmask, int B,
+                           int H, int W, int Hf, int Wf, mhada_stream_t stream);
+
 /* ---- training path (train_image.py:139 loss.backward(), fp32, NHWC activations) ---------- */
 
 /* Weight-gradient contraction C[M][N] = sum_k A[k][m] * B[k][n] (C row stride ldc), fp32:

@@ -13,59 +13,9 @@
 // partial sums (deterministic).
 // Layouts are the reference's: NCHW fp32 images/features, flow [B][2][H][W] (x then y).
 #include "common.h"
+#include "warp_tap.h"
 
 namespace mhada {
-
-struct Tap {
-  int x0, y0;
-  float wnw, wne, wsw, wse;
-  bool inw, ine, isw, ise;
-};
-
-// Sample position of output pixel (x, y) displaced by (fx, fy); padding 0 zeros, 1 border.
-MHADA_DEV Tap warp_tap(int x, int y, float fx, float fy, int H, int W, int padding) {
-  const float dx = (float)(W - 1 > 1 ? W - 1 : 1), dy = (float)(H - 1 > 1 ? H - 1 : 1);
-  // vgrid normalisation (utilities.py:112-113), one rounding per tensor op
-  float gx = 2.0f * ((float)x + fx);
-  gx = gx / dx;
-  gx = gx - 1.0f;
-  float gy = 2.0f * ((float)y + fy);
-  gy = gy / dy;
-  gy = gy - 1.0f;
-  // grid_sampler_unnormalize, align_corners=False
-  float ix = ((gx + 1.f) * (float)W - 1.f) / 2.f;
-  float iy = ((gy + 1.f) * (float)H - 1.f) / 2.f;
-  if (padding == 1) {  // border: clip_coordinates
-    ix = fminf(fmaxf(ix, 0.f), (float)(W - 1));
-    iy = fminf(fmaxf(iy, 0.f), (float)(H - 1));
-  }
-  const float fx0 = floorf(ix), fy0 = floorf(iy);
-  Tap t;
-  t.x0 = (int)fx0;
-  t.y0 = (int)fy0;
-  const float ix_se = fx0 + 1.f, iy_se = fy0 + 1.f;
-  t.wnw = (ix_se - ix) * (iy_se - iy);
-  t.wne = (ix - fx0) * (iy_se - iy);
-  t.wsw = (ix_se - ix) * (iy - fy0);
-  t.wse = (ix - fx0) * (iy - fy0);
-  const bool x0in = t.x0 >= 0 && t.x0 < W, x1in = t.x0 + 1 >= 0 && t.x0 + 1 < W;
-  const bool y0in = t.y0 >= 0 && t.y0 < H, y1in = t.y0 + 1 >= 0 && t.y0 + 1 < H;
-  t.inw = x0in && y0in;
-  t.ine = x1in && y0in;
-  t.isw = x0in && y1in;
-  t.ise = x1in && y1in;
-  return t;
-}
-
-MHADA_DEV float sample(const float* plane, const Tap& t, int W) {
-  float acc = 0.f;
-  const long long o = (long long)t.y0 * W + t.x0;
-  if (t.inw) acc += plane[o] * t.wnw;
-  if (t.ine) acc += plane[o + 1] * t.wne;
-  if (t.isw) acc += plane[o + W] * t.wsw;
-  if (t.ise) acc += plane[o + W + 1] * t.wse;
-  return acc;
-}
 
 __global__ void __launch_bounds__(256) warp_kernel(const float* __restrict__ x, const float* __restrict__ flow,
                                                    float* __restrict__ y, int C, int H, int W, int padding) {

@@ -110,6 +110,9 @@ SIGNATURES = {
     "mhada_warp_bwd": (_I, [_vp, _vp, _vp, _I, _I, _I, _I, _I, _vp]),
     "mhada_flow_warp_mask": (_I, [_vp, _vp, _vp, _I, _I, _F, _I, _vp]),
     "mhada_warp_l1": (_I, [_vp, _vp, _vp, _vp, _vp, _vp, _I, _I, _I, _I, _vp]),
+    "mhada_temporal_loss_fwd": (_I, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _I, _I, _I, _I, _vp]),
+    "mhada_temporal_loss_bwd": (_I, [_vp] * 14 + [_I, _I, _I, _I, _vp]),
+    "mhada_flow_mask_resize": (_I, [_vp, _vp, _vp, _vp, _I, _I, _I, _I, _I, _vp]),
     "mhada_frame_ingest": (_I, [_vp, _I, _I, _I, _c_ll, _I, _vp, _I, _I, _vp]),
     "mhada_frame_emit": (_I, [_vp, _I, _I, _I, _vp, _c_ll, _I, _vp]),
     "mhada_conv3x3_out3_u8": (_I, [_vp, _I, _vp, _vp, _vp, _c_ll, _I, _I, _I, _I, _I, _vp]),

@@ -1508,6 +1508,99 @@ def warp_l1(cs1: torch.Tensor, cs2: torch.Tensor, flow: torch.Tensor, mask: torc
     return out
 
 
+# ---- video path: the temporal losses of train_video.py (csrc/temporal.hip) ------------------
+TEMPORAL_WORK_WORDS = 1 + 2 * 2048  # MHADA_TEMPORAL_WORK_WORDS
+
+
+def _strides4(t: torch.Tensor):
+    """The element strides {b, c, y, x} of a 4-d tensor as the host array the temporal entries read."""
+    return (ctypes.c_longlong * 4)(*t.stride())
+
+
+def _temporal_args(x1, x2, flow, m, c1, c2, what):
+    _need_gpu(x1, x2, flow, m)
+    if x1.dim() != 4 or x1.shape != x2.shape or x1.dtype != torch.float32 or x2.dtype != torch.float32:
+        raise ValueError(f"{what}: x1 / x2 must be float32 [B,C,H,W] of one shape")
+    B, C, H, W = x1.shape
+    flow, m = _f32c(flow, "flow"), _f32c(m, "mask")
+    if tuple(flow.shape) != (B, 2, H, W) or tuple(m.shape) != (B, H, W):
+        raise ValueError(f"{what}: flow [B,2,H,W] and mask [B,H,W] must match x1 {list(x1.shape)}")
+    if (c1 is None) != (c2 is None):
+        raise ValueError(f"{what}: c1 and c2 go together")
+    if c1 is not None:
+        _need_gpu(c1, c2)
+        c1, c2 = _f32c(c1, "c1"), _f32c(c2, "c2")
+        if tuple(c1.shape) != (B, 3, H, W) or c2.shape != c1.shape:
+            raise ValueError(f"{what}: c1 / c2 must be [B,3,H,W] = {[B, 3, H, W]}")
+    if any(s < 0 for s in x1.stride() + x2.stride()):
+        raise ValueError(f"{what}: negative strides")
+    return flow, m, c1, c2
+
+
+def temporal_loss_fwd(x1: torch.Tensor, x2: torch.Tensor, flow: torch.Tensor, m: torch.Tensor,
+                      c1: Optional[torch.Tensor] = None, c2: Optional[torch.Tensor] = None):
+    """``mhada_temporal_loss_fwd``: sum(m (x2 - warp(x1, flow) - t)^2) / (C #{m != 0}) as a 0-d device
+    tensor, with no host synchronisation; t = the luminance of c2 - warp(c1, flow) when c1 / c2 are
+    given (lossfn.py:50-66), else 0 (lossfn.py:81-86).  x1 / x2 [B,C,H,W] in any strided layout
+    (contiguous NCHW or channels_last: no copy).  Returns (loss, work); ``work`` (int64, word 0 the
+    count of m != 0) is what ``temporal_loss_bwd`` takes."""
+    flow, m, c1, c2 = _temporal_args(x1, x2, flow, m, c1, c2, "temporal_loss_fwd")
+    B, C, H, W = x1.shape
+    work = torch.empty(TEMPORAL_WORK_WORDS, device=x1.device, dtype=torch.int64)
+    out = torch.empty((), device=x1.device, dtype=torch.float32)
+    _call("mhada_temporal_loss_fwd", x1, x1.data_ptr(), _strides4(x1), x2.data_ptr(), _strides4(x2), flow.data_ptr(),
+          m.data_ptr(), None if c1 is None else c1.data_ptr(), None if c2 is None else c2.data_ptr(),
+          work.data_ptr(), out.data_ptr(), B, C, H, W)
+    return out, work
+
+
+def temporal_loss_bwd(x1: torch.Tensor, x2: torch.Tensor, flow: torch.Tensor, m: torch.Tensor,
+                      c1: Optional[torch.Tensor], c2: Optional[torch.Tensor], work: torch.Tensor, g: torch.Tensor,
+                      need_dx1: bool = True, need_dx2: bool = True, dx1: Optional[torch.Tensor] = None,
+                      dx2: Optional[torch.Tensor] = None):
+    """``mhada_temporal_loss_bwd``: (dx1, dx2) of ``temporal_loss_fwd`` for the upstream gradient g (a
+    device scalar; no synchronisation) and the forward's ``work``.  dx2 is deterministic; dx1 is an
+    atomic scatter like ``warp_bwd``'s.  ``dx1`` (ZEROED) / ``dx2`` may be given as [B,C,H,W] float32
+    tensors of any strides; by default they take x1's / x2's layout."""
+    flow, m, c1, c2 = _temporal_args(x1, x2, flow, m, c1, c2, "temporal_loss_bwd")
+    B, C, H, W = x1.shape
+    g = g.to(torch.float32).reshape(1)
+    if work.dtype != torch.int64 or work.numel() < 1 or not work.is_contiguous():
+        raise ValueError("temporal_loss_bwd: work must be temporal_loss_fwd's int64 workspace")
+    if need_dx1 and dx1 is None:
+        dx1 = torch.zeros_like(x1)
+    if need_dx2 and dx2 is None:
+        dx2 = torch.empty_like(x2)
+    for d in (dx1, dx2):
+        if d is not None and (d.shape != x1.shape or d.dtype != torch.float32 or d.device != x1.device
+                              or any(s < 0 for s in d.stride())):
+            raise ValueError("temporal_loss_bwd: dx1 / dx2 must be float32 [B,C,H,W] like x1 on its device")
+    if dx1 is None and dx2 is None:
+        return None, None
+    _call("mhada_temporal_loss_bwd", x1, x1.data_ptr(), _strides4(x1), x2.data_ptr(), _strides4(x2), flow.data_ptr(),
+          m.data_ptr(), None if c1 is None else c1.data_ptr(), None if c2 is None else c2.data_ptr(),
+          work.data_ptr(), g.data_ptr(), None if dx1 is None else dx1.data_ptr(),
+          None if dx1 is None else _strides4(dx1), None if dx2 is None else dx2.data_ptr(),
+          None if dx2 is None else _strides4(dx2), B, C, H, W)
+    return dx1, dx2
+
+
+def flow_mask_resize(flow: torch.Tensor, mask: torch.Tensor, size):
+    """``mhada_flow_mask_resize`` (lossfn.py:71-80): flow [B,2,H,W], mask [B,H,W] -> (the flow resized
+    bilinearly to ``size`` = (Hf, Wf) and scaled to that grid, (the resized mask > 0) as floats)."""
+    _need_gpu(flow, mask)
+    flow, mask = _f32c(flow, "flow"), _f32c(mask, "mask")
+    if flow.dim() != 4 or flow.shape[1] != 2 or tuple(mask.shape) != (flow.shape[0],) + tuple(flow.shape[2:]):
+        raise ValueError("flow_mask_resize: flow [B,2,H,W], mask [B,H,W]")
+    B, _, H, W = flow.shape
+    Hf, Wf = int(size[0]), int(size[1])
+    fflow = torch.empty(B, 2, Hf, Wf, device=flow.device, dtype=torch.float32)
+    fmask = torch.empty(B, Hf, Wf, device=flow.device, dtype=torch.float32)
+    _call("mhada_flow_mask_resize", flow, flow.data_ptr(), mask.data_ptr(), fflow.data_ptr(), fmask.data_ptr(),
+          B, H, W, Hf, Wf)
+    return fflow, fmask
+
+
 def frame_ingest(frames: torch.Tensor, out_hw=None, bgr: bool = True) -> torch.Tensor:
     """``mhada_frame_ingest``: u8 frames [B][H][W][3] (or one [H][W][3]; rows may be padded) ->
     fp32 [B][3][Ho][Wo] (BGR->RGB, INTER_AREA to out_hw = (Ho, Wo), toTensor255)."""

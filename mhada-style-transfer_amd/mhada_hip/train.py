@@ -210,8 +210,9 @@ class VideoTrainer(Trainer):
     """One iteration of ``train_video.py:110-171`` (fine-tuning on frame pairs with optical flow):
     5 AdaFormer calls (cs1, cs2, cc1, cc2, ss), VGG19 of the 3 inputs (no grad) and the 5 outputs,
     global-style / local-feature losses of both frames, the output- and feature-level temporal
-    losses (lossfn.py:50-86: the warps and their adjoints on HIP, video.WarpFn), identity losses,
-    weighted 100 / 15 / 2 / 2 / 0.05 / 0.1.
+    losses (lossfn.py:50-86: each one fused masked, warped MSE on HIP without a host synchronisation,
+    video.TemporalLossFn; with ``fused_temporal_losses`` unset the aten chain around video.WarpFn),
+    identity losses, weighted 100 / 15 / 2 / 2 / 0.05 / 0.1.
 
         trainer = VideoTrainer(vit_c, vit_s, ada, vgg)
         losses = trainer.step(style, c1, c2, flow, mask)   # the data loader's tuple order
@@ -219,6 +220,12 @@ class VideoTrainer(Trainer):
     Data parallel as Trainer (gradient all-reduce = mean over ranks); the temporal losses normalise
     by each rank's own nonzero-mask count, so N ranks equal one process only when the counts match
     (the reference trains video on one GPU)."""
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        # the two temporal losses on video.TemporalLossFn (HIP, csrc/temporal.hip): the mask count is
+        # reduced on the device, so the forward no longer stops twice for torch.nonzero(m).shape[0]
+        self.fused_temporal_losses = next(self.vit_c.parameters()).device.type == "cuda"
 
     def video_losses(self, style, c1, c2, flow, mask) -> Dict[str, torch.Tensor]:
         """train_video.py:110-166.  As in Trainer.losses, calls of one module on inputs of one shape
@@ -249,9 +256,14 @@ class VideoTrainer(Trainer):
                 k = f"relu{i}_1"
                 id2 = id2 + self.mse(vgg_fcc1[k], vgg_fc1[k]) + self.mse(vgg_fcc2[k], vgg_fc2[k]) \
                     + self.mse(vgg_fss[k], vgg_fs[k])
-        mse_matrix = nn.MSELoss(reduction="none")
-        ot = L.output_level_temporal_loss(c1, c2, cs1, cs2, flow, mask, mse_matrix) * VIDEO_LAMBDA_OT
-        ft = L.feature_level_temporal_loss(ada_fcs1, ada_fcs2, flow, mask, mse_matrix) * VIDEO_LAMBDA_FT
+        if self.fused_temporal_losses:
+            from .video import feature_level_temporal_loss_hip, output_level_temporal_loss_hip
+            ot = output_level_temporal_loss_hip(c1, c2, cs1, cs2, flow, mask) * VIDEO_LAMBDA_OT
+            ft = feature_level_temporal_loss_hip(ada_fcs1, ada_fcs2, flow, mask) * VIDEO_LAMBDA_FT
+        else:
+            mse_matrix = nn.MSELoss(reduction="none")
+            ot = L.output_level_temporal_loss(c1, c2, cs1, cs2, flow, mask, mse_matrix) * VIDEO_LAMBDA_OT
+            ft = L.feature_level_temporal_loss(ada_fcs1, ada_fcs2, flow, mask, mse_matrix) * VIDEO_LAMBDA_FT
         id1 = (self.mse(cc1, c1) + self.mse(cc2, c2) + self.mse(ss, style)) * VIDEO_LAMBDA_ID1
         gs, lf, id2 = gs * VIDEO_LAMBDA_GS, lf * VIDEO_LAMBDA_LF, id2 * VIDEO_LAMBDA_ID2
         return {"loss_gs": gs, "loss_lf": lf, "loss_ot": ot, "loss_ft": ft, "loss_id1": id1, "loss_id2": id2,

@@ -54,6 +54,60 @@ def warp(x: torch.Tensor, flo: torch.Tensor, padding_mode: str = "zeros") -> tor
     return ops.warp(x, flo, padding_mode)
 
 
+class TemporalLossFn(torch.autograd.Function):
+    """One masked, warped MSE of train_video.py's temporal losses (lossfn.py:50-86),
+    sum(m (x2 - warp(x1, flow) - t)^2) / (C #{m != 0}), as two HIP launches forward
+    (mhada_temporal_loss_fwd: the sum and the count reduced on the device, no host synchronisation)
+    and one backward (mhada_temporal_loss_bwd).  t is the luminance of c2 - warp(c1, flow) when
+    c1 / c2 are given, else 0.  Saves its inputs and the kernel's small workspace only; flow, m, c1
+    and c2 are data (no gradient)."""
+
+    @staticmethod
+    def forward(ctx, x1, x2, flow, m, c1, c2):
+        out, work = ops.temporal_loss_fwd(x1, x2, flow, m, c1, c2)
+        ctx.save_for_backward(x1, x2, flow, m, c1, c2, work)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        x1, x2, flow, m, c1, c2, work = ctx.saved_tensors
+        dx1, dx2 = ops.temporal_loss_bwd(x1, x2, flow, m, c1, c2, work, g, need_dx1=ctx.needs_input_grad[0],
+                                         need_dx2=ctx.needs_input_grad[1])
+        return dx1, dx2, None, None, None, None
+
+
+def _temporal_fused(images, data) -> bool:
+    """The fused route takes float32 device tensors whose data operands (flow, mask, frames) take no
+    gradient; everything else evaluates the expressions of mhada_hip.losses."""
+    if not all(t.is_cuda and t.dtype == torch.float32 for t in tuple(images) + tuple(data)):
+        return False
+    return not (torch.is_grad_enabled() and any(t.requires_grad for t in data))
+
+
+def output_level_temporal_loss_hip(c1, c2, cs1, cs2, flow, mask) -> torch.Tensor:
+    """lossfn.output_level_temporal_loss (lossfn.py:50-66) with nn.MSELoss(reduction="none") as its
+    loss matrix, as a 0-d device tensor computed by TemporalLossFn without a host synchronisation
+    (the reference's, and mhada_hip.losses', torch.nonzero(m).shape[0] is one).  An all-zero mask gives
+    NaN where the reference raises ZeroDivisionError.  CPU tensors, or a flow / mask / c1 / c2 that
+    takes a gradient, evaluate mhada_hip.losses.output_level_temporal_loss."""
+    if not _temporal_fused((cs1, cs2), (c1, c2, flow, mask)):
+        return losses.output_level_temporal_loss(c1, c2, cs1, cs2, flow, mask, torch.nn.MSELoss(reduction="none"))
+    if c2.shape[1] > 3:  # the luminance reads channels 0..2 (lossfn.py:53)
+        c1, c2 = c1[:, :3], c2[:, :3]
+    return TemporalLossFn.apply(cs1, cs2, flow, mask, c1, c2)
+
+
+def feature_level_temporal_loss_hip(f1, f2, flow, mask) -> torch.Tensor:
+    """lossfn.feature_level_temporal_loss (lossfn.py:69-86) with nn.MSELoss(reduction="none"): the flow
+    and the mask resized to the feature grid by one launch (mhada_flow_mask_resize), then
+    TemporalLossFn on f1 / f2 in their own layout (channels_last views are not copied).  Same
+    conventions as output_level_temporal_loss_hip."""
+    if not _temporal_fused((f1, f2), (flow, mask)):
+        return losses.feature_level_temporal_loss(f1, f2, flow, mask, torch.nn.MSELoss(reduction="none"))
+    fflow, fmask = ops.flow_mask_resize(flow, mask, f1.shape[2:])
+    return TemporalLossFn.apply(f1, f2, fflow, fmask, None, None)
+
+
 def cv2_to_tensor(img, resize: Optional[tuple] = None, device: Optional[torch.device] = None) -> torch.Tensor:
     """utilities.cv2_to_tensor: ``img`` is a cv2 BGR u8 frame (H, W, 3) — a numpy array (uploaded
     through pinned memory to ``device``, default the current ROCm device) or a uint8 device

@@ -3,7 +3,7 @@ adjoint, backward, 3 Adam steps) at the script's shapes — 2 frame pairs of 256
 style (train_video.py:15-29, datasets.py:374-378) — timed with HIP events after warmup; synthetic
 frames, a smooth random flow and a random consistency mask.
 
-    python tools/video_train_time.py [steps] [warmup]
+    python tools/video_train_time.py [steps] [warmup] [fused_temporal_losses: 1 (default) | 0]
 """
 import os
 import sys
@@ -29,6 +29,8 @@ def main():
     ada = load_recipe(network.AdaAttnTransformerMultiHead(), "ada").to(dev).train()
     vgg = load_recipe(network.VGG19(), "vgg").to(dev)
     tr = VideoTrainer(vc, vs, ada, vgg)
+    if len(sys.argv) > 3:
+        tr.fused_temporal_losses = bool(int(sys.argv[3]))
     B, H, W = 2, 256, 512
     style = seeded_image(B, 256, 256, 1).to(dev)
     c1 = seeded_image(B, H, W, 2).to(dev)
@@ -48,7 +50,8 @@ def main():
     e.record()
     torch.cuda.synchronize()
     wall = (time.perf_counter() - t0) / steps * 1e3
-    print(f"train_video step (B=2 frame pairs 256x512, style 256x256): {s.elapsed_time(e) / steps:.1f} ms/step "
+    print(f"train_video step (B=2 frame pairs 256x512, style 256x256, fused_temporal_losses "
+          f"{int(tr.fused_temporal_losses)}): {s.elapsed_time(e) / steps:.1f} ms/step "
           f"(wall {wall:.1f}); losses " + " ".join(f"{k} {v:.4g}" for k, v in out.items()), flush=True)
 
 
