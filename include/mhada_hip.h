@@ -328,6 +328,45 @@ int mhada_attn_split3_planes(const float* q, const void* img, const float* fcs, 
                              const float* fcs_rstd, const float* v_mu, void* planes, int B, int H, int Nc, int Ns,
                              mhada_stream_t stream);
 
+/* ---- clips: B content frames against ONE style (additive to ABI 18, found by symbol) ---------------
+ * The shared-style forms of mhada_attn (softmax; fp32 and bf16), mhada_attn_split3 and
+ * mhada_attn_split3_planes at head width 64: q [B][H][Nc][64], fcs [B][Nc][64H], fcs_mu / fcs_rstd [B][64H]
+ * and out ([B][Nc][64H], or the planes [3][B Nc][64H]) are per frame; kv [H][Ns][128], vt [H][128][ldt],
+ * img [H][576 ldt] and v_mu [64H] belong to one style, which every frame attends to.  Each frame's result
+ * is bit-identical to the per-batch entry called with the style operands repeated B times (the same
+ * kernel forms, chosen by the same rules, with a zero batch stride on the style operands).  The fold for
+ * this case is mhada_fold_block itself: called with the style statistics repeated B times it gives wq per
+ * frame, and wkv[0], v_mu[0] are the one style's. */
+int mhada_attn_shared(const void* q, const void* kv, const void* vt, const float* fcs,
+                      const float* fcs_mu, const float* fcs_rstd, const float* v_mu, void* out,
+                      int dtype, int B, int H, int Nc, int Ns, int activation, mhada_stream_t stream);
+int mhada_attn_split3_shared(const float* q, const void* img, const float* fcs, const float* fcs_mu,
+                             const float* fcs_rstd, const float* v_mu, float* out, int B, int H, int Nc, int Ns,
+                             mhada_stream_t stream);
+int mhada_attn_split3_planes_shared(const float* q, const void* img, const float* fcs, const float* fcs_mu,
+                                    const float* fcs_rstd, const float* v_mu, void* planes, int B, int H, int Nc,
+                                    int Ns, mhada_stream_t stream);
+/* mhada_vit_batch_attn, _split3 and _half2 with the L images taken as `groups` independent calls of
+ * L / groups images each, in one launch; bit-identical to the ungrouped entry on each group's slice.
+ * Built for L / groups == 1 only (one image per call: the softmax over one key is exactly 1 and the output is
+ * V, or V's planes, bit for bit on finite inputs), where it is the ungrouped entry at L = 1 over L * ntok
+ * tokens; any other L / groups returns MHADA_ERR_ARG. */
+int mhada_vit_batch_attn_grouped(const void* qkv, void* out, int dtype, int L, int ntok, int heads,
+                                 int head_dim, int groups, mhada_stream_t stream);
+int mhada_vit_batch_attn_split3_grouped(const float* qkv, void* planes, long long pstride, int L, int ntok,
+                                        int heads, int head_dim, int groups, mhada_stream_t stream);
+int mhada_vit_batch_attn_half2_grouped(const float* qkv, void* planes, long long pstride, const float* out_scale,
+                                       int L, int ntok, int heads, int head_dim, int groups,
+                                       mhada_stream_t stream);
+
+/* Form routing for chunked calls: the dispatch rules that choose a kernel form from the rows or the batch of
+ * a call (mhada_gemm's fp32 tile-fill rule, the waves per block of mhada_attn* ) evaluate x * mul / div in
+ * place of x, so that a chunk of `div` frames takes the forms a clip of `mul` frames takes and a frame's bits
+ * do not depend on how the clip was cut into chunks.  mul = div = 0 (the default) turns it off.  Process-wide,
+ * like mhada_set_tuning; every kernel form is valid at every size, so the setting changes speed and rounding
+ * order only. */
+int mhada_set_route(int mul, int div);
+
 /* The cosine activation (CosineSimilarity, adaDecoder.py:20-34) in its linear form (ABI 14):
  * A[i][j] = (q^_i.k^_j + 1) / l_i with l_i = q^_i.sum_j k^_j + Ns, so A V' and A V'^2 need only the
  * style-side moments — O(N d^2) instead of mhada_attn's Nc x Ns loop.  After mhada_cosine_prep:

@@ -120,8 +120,12 @@ __global__ void __launch_bounds__(256) train_vt_kernel(const float* __restrict__
 // K rows of p.ldk = 64 floats (the training k), Q scaled by log2 e on load (the training q is in
 // natural units), and the training epilogue (attn_train_epilogue: out', [M' | E2'], lse2 =
 // m2 + log2 l, exact for the lazily rescaled state since l is relative to m2).
-template <int ACT, int NW, bool TRAIN = false>
+// SHARED (ACTF = ACT | kAttnShared; mhada_attn_shared): kv / vt / v_mu belong to ONE style that every
+// frame b attends to; everything else, and so every frame's bits, as the per-batch form.
+template <int ACTF, int NW, bool TRAIN = false>
 __global__ void __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) attn_f32_kernel(const AttnP p) {
+  constexpr int ACT = ACTF & ~kAttnShared;
+  constexpr bool SHARED = (ACTF & kAttnShared) != 0;
   constexpr int NT = 64 * NW;
   constexpr int LK = 68, LV = 68;  // padded rows (272 B): conflict-free 16-B reads down a column
   constexpr int KCH = 1024 / NT, VCH = 2048 / NT;  // 16-B chunks per thread per 64-key tile
@@ -146,8 +150,9 @@ __global__ void __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) attn_f32_kernel(cons
     }
   }
   const int ldk = TRAIN ? 64 : 128;
-  const float* kvb = reinterpret_cast<const float*>(p.kv) + bh * p.Ns * ldk;
-  const float* vtb = reinterpret_cast<const float*>(p.vt) + bh * 128 * (long long)p.ldt;
+  const long long sbh = SHARED ? hh : bh;  // the style operands' problem index
+  const float* kvb = reinterpret_cast<const float*>(p.kv) + sbh * p.Ns * ldk;
+  const float* vtb = reinterpret_cast<const float*>(p.vt) + sbh * 128 * (long long)p.ldt;
 
   // K rows from kv, V'^T | V'^2^T columns from the vt image (mhada_transpose_v, zero padded to
   // ldt): the PV operands are then one 16-B LDS read per 4 MFMAs with no VALU (reading V' rows
@@ -266,14 +271,17 @@ __global__ void __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) attn_f32_kernel(cons
   }
   ATTN_STAMP(1);
   if constexpr (TRAIN) attn_train_epilogue(p, O, l, m2, bh, q, h);
-  else attn_epilogue<float>(p, O, l, b, hh, q, h);
+  else attn_epilogue<float, SHARED>(p, O, l, b, hh, q, h);
 }
 
 // ======================================================================================
 // bf16 variant
 // ======================================================================================
-template <int ACT, int NW, int TK>
+// ACTF = ACT | kAttnShared selects the shared-style form (attn_common.h), as in attn_f32_kernel.
+template <int ACTF, int NW, int TK>
 __global__ void __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) attn_bf16_kernel(const AttnP p) {
+  constexpr int ACT = ACTF & ~kAttnShared;
+  constexpr bool SHARED = (ACTF & kAttnShared) != 0;
   constexpr int NT = 64 * NW, NKB = TK / 32;
   constexpr int LK = 72;       // K rows: 64 + 8 bf16 (144 B): conflict-free 16-B row reads
   constexpr int LV = TK + 8;   // V'^T rows: TK keys + 8 (row stride = 16 B mod 256 B): conflict-free
@@ -301,8 +309,9 @@ __global__ void __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) attn_bf16_kernel(con
       }
     }
   }
-  const bf16* kvb = reinterpret_cast<const bf16*>(p.kv) + bh * p.Ns * 128;
-  const bf16* vtb = reinterpret_cast<const bf16*>(p.vt) + bh * 128 * (long long)p.ldt;
+  const long long sbh = SHARED ? hh : bh;  // the style operands' problem index
+  const bf16* kvb = reinterpret_cast<const bf16*>(p.kv) + sbh * p.Ns * 128;
+  const bf16* vtb = reinterpret_cast<const bf16*>(p.vt) + sbh * 128 * (long long)p.ldt;
 
   bf16x8 sk[KCH], sv[VCH];
   auto issue = [&](int key0) {
@@ -417,7 +426,7 @@ __global__ void __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) attn_bf16_kernel(con
     if (softmax_tile<ACT, NKB>(S, m2, l, alpha)) scale_acc(O, alpha);
     pv(sV[cb], S);
   }
-  attn_epilogue<bf16>(p, O, l, b, hh, q, h);
+  attn_epilogue<bf16, SHARED>(p, O, l, b, hh, q, h);
 }
 
 // --------------------------------------------------------------------------------------
@@ -430,8 +439,11 @@ __global__ void __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) attn_bf16_kernel(con
 // (attn_exact_half).  Branch-free clamped tile loads (keys past Ns re-read valid rows and are
 // masked in the last tile).
 // --------------------------------------------------------------------------------------
-template <int NW, int TK>
+// TKF = TK | kAttnShared selects the shared-style form (attn_common.h): <8, 384> is TK 128 against one style.
+template <int NW, int TKF>
 __global__ void __launch_bounds__(64 * NW, 1) attn_bf16_fs_kernel(const AttnP p) {
+  constexpr int TK = TKF & ~kAttnShared;
+  constexpr bool SHARED = (TKF & kAttnShared) != 0;
   constexpr int NT = 64 * NW, NKB = TK / 32;
   constexpr int LK = 72, LV = TK + 8;  // padded rows: conflict-free 16-B reads
   constexpr int KSZ = TK * LK, VSZ = 128 * LV;
@@ -459,8 +471,9 @@ __global__ void __launch_bounds__(64 * NW, 1) attn_bf16_fs_kernel(const AttnP p)
       }
     }
   }
-  const bf16* kvb = reinterpret_cast<const bf16*>(p.kv) + bh * (long long)Ns * 128;
-  const bf16* vtb = reinterpret_cast<const bf16*>(p.vt) + bh * 128 * (long long)p.ldt;
+  const long long sbh = SHARED ? hh : bh;  // the style operands' problem index
+  const bf16* kvb = reinterpret_cast<const bf16*>(p.kv) + sbh * (long long)Ns * 128;
+  const bf16* vtb = reinterpret_cast<const bf16*>(p.vt) + sbh * 128 * (long long)p.ldt;
 
   bf16x8 sk[KCH], sv[VCH];
   auto issue = [&](int key0) {  // clamped: past-the-end rows / columns re-read valid data
@@ -572,7 +585,7 @@ __global__ void __launch_bounds__(64 * NW, 1) attn_bf16_fs_kernel(const AttnP p)
   }
   const float lt = l + __shfl_xor(l, 32, 64);
   if (__any(!(lt <= kShiftSumThr))) attn_exact_half(p, kvb, vtb, qf, O, l, h, r32);
-  attn_epilogue<bf16>(p, O, l, b, hh, q, h);
+  attn_epilogue<bf16, SHARED>(p, O, l, b, hh, q, h);
 }
 
 // --------------------------------------------------------------------------------------
@@ -670,8 +683,11 @@ MHADA_DEV void attn_exact_q(const AttnP& p, const bf16* kvb, const bf16* vtb, co
   }
 }
 
-template <int NW>
-__global__ void __launch_bounds__(64 * NW, 1) attn_bf16_fsq_kernel(const AttnP p) {
+// NWF = NW | kAttnShared selects the shared-style form (attn_common.h): <260> / <264> are 4 / 8 waves against one style.
+template <int NWF>
+__global__ void __launch_bounds__(64 * (NWF & ~kAttnShared), 1) attn_bf16_fsq_kernel(const AttnP p) {
+  constexpr int NW = NWF & ~kAttnShared;
+  constexpr bool SHARED = (NWF & kAttnShared) != 0;
   constexpr int TK = 128, NSL = 2;
   constexpr int KSZ = TK * 64, VSZ = 128 * TK;  // bf16 elements per slot: K [128][64], V'^T [128][128]
   constexpr int KPW = TK * 128 / 1024 / NW, VPW = 128 * TK * 2 / 1024 / NW;  // 1-KiB pieces per wave
@@ -700,8 +716,9 @@ __global__ void __launch_bounds__(64 * NW, 1) attn_bf16_fsq_kernel(const AttnP p
       }
     }
   }
-  const bf16* kvb = reinterpret_cast<const bf16*>(p.kv) + bh * (long long)Ns * 128;
-  const bf16* vtb = reinterpret_cast<const bf16*>(p.vt) + bh * 128 * (long long)p.ldt;
+  const long long sbh = SHARED ? hh : bh;  // the style operands' problem index
+  const bf16* kvb = reinterpret_cast<const bf16*>(p.kv) + sbh * (long long)Ns * 128;
+  const bf16* vtb = reinterpret_cast<const bf16*>(p.vt) + sbh * 128 * (long long)p.ldt;
   int ksrc[KPW], vsrc[VPW];
 #pragma unroll
   for (int i = 0; i < KPW; ++i) {
@@ -824,7 +841,7 @@ __global__ void __launch_bounds__(64 * NW, 1) attn_bf16_fsq_kernel(const AttnP p
 #pragma unroll
   for (int qg = 0; qg < 2; ++qg) lt[qg] = L[qg][0];  // every D row is the full sum over the 32 keys of each MFMA
   if (__any(!(lt[0] <= kShiftSumThr) || !(lt[1] <= kShiftSumThr))) attn_exact_q(p, kvb, vtb, qf, O, lt, g, r16);
-  attn_epilogue_q<bf16>(p, O, lt, b, hh, q0, g, r16);
+  attn_epilogue_q<bf16, false, SHARED>(p, O, lt, b, hh, q0, g, r16);
 }
 
 // Variant selection: the fixed-shift kernels are the bf16 softmax default (fsq1 when Ns % 128 == 0,
@@ -835,11 +852,15 @@ __global__ void __launch_bounds__(64 * NW, 1) attn_bf16_fsq_kernel(const AttnP p
 static bool attn_bf16_fixed_shift() { return tuning().attn_fixed_shift != 0; }
 static int attn_tk() { return tuning().attn_tk; }
 
-template <int NW>
+// SHARED: the shared-style kernels (softmax only), chosen by the same rules, so a frame runs the kernel
+// form it would run through mhada_attn at the same B.
+template <int NW, bool SHARED = false>
 static void launch_attn(const AttnP& p, int dtype, int activation, hipStream_t s) {
   const dim3 grid(p.nblk), blk(64 * NW);
   if (dtype == MHADA_F32) {
-    if (activation == MHADA_ACT_SOFTMAX)
+    if constexpr (SHARED)
+      hipLaunchKernelGGL((attn_f32_kernel<MHADA_ACT_SOFTMAX | kAttnShared, NW>), grid, blk, 0, s, p);
+    else if (activation == MHADA_ACT_SOFTMAX)
       hipLaunchKernelGGL((attn_f32_kernel<MHADA_ACT_SOFTMAX, NW>), grid, blk, 0, s, p);
     else
       hipLaunchKernelGGL((attn_f32_kernel<MHADA_ACT_COSINE, NW>), grid, blk, 0, s, p);
@@ -847,16 +868,21 @@ static void launch_attn(const AttnP& p, int dtype, int activation, hipStream_t s
   }
   if (activation == MHADA_ACT_SOFTMAX && attn_bf16_fixed_shift()) {
     if (p.Ns % 128 == 0) {  // whole 128-key tiles: the LDS-DMA 16x16x32 kernel
-      hipLaunchKernelGGL((attn_bf16_fsq_kernel<NW>), grid, blk, 0, s, p);
+      if constexpr (SHARED) hipLaunchKernelGGL((attn_bf16_fsq_kernel<NW | kAttnShared>), grid, blk, 0, s, p);
+      else hipLaunchKernelGGL((attn_bf16_fsq_kernel<NW>), grid, blk, 0, s, p);
       return;
     }
     if constexpr (NW == 8) {  // ragged Ns: register-staged fixed shift (2 x 106 KiB at 4 waves does not fit)
-      hipLaunchKernelGGL((attn_bf16_fs_kernel<8, 128>), grid, blk, 0, s, p);
+      if constexpr (SHARED) hipLaunchKernelGGL((attn_bf16_fs_kernel<8, 128 | kAttnShared>), grid, blk, 0, s, p);
+      else hipLaunchKernelGGL((attn_bf16_fs_kernel<8, 128>), grid, blk, 0, s, p);
       return;
     }
   }
   const bool t128 = NW == 8 && attn_tk() == 128;  // 2 x 106 KiB of LDS does not fit a CU
-  if (activation == MHADA_ACT_SOFTMAX) {
+  if constexpr (SHARED) {
+    if (t128) hipLaunchKernelGGL((attn_bf16_kernel<MHADA_ACT_SOFTMAX | kAttnShared, NW, (NW == 8 ? 128 : 64)>), grid, blk, 0, s, p);
+    else hipLaunchKernelGGL((attn_bf16_kernel<MHADA_ACT_SOFTMAX | kAttnShared, NW, 64>), grid, blk, 0, s, p);
+  } else if (activation == MHADA_ACT_SOFTMAX) {
     if (t128) hipLaunchKernelGGL((attn_bf16_kernel<MHADA_ACT_SOFTMAX, NW, (NW == 8 ? 128 : 64)>), grid, blk, 0, s, p);
     else hipLaunchKernelGGL((attn_bf16_kernel<MHADA_ACT_SOFTMAX, NW, 64>), grid, blk, 0, s, p);
   } else {
@@ -869,14 +895,17 @@ static void launch_attn(const AttnP& p, int dtype, int activation, hipStream_t s
 
 using namespace mhada;
 
-extern "C" int mhada_attn(const void* q, const void* kv, const void* vt, const float* fcs, const float* fcs_mu,
-                          const float* fcs_rstd, const float* v_mu, void* out, int dtype, int B, int H, int Nc,
-                          int Ns, int activation, mhada_stream_t s_) {
+template <bool SHARED>
+static int attn_entry(const char* name, const void* q, const void* kv, const void* vt, const float* fcs,
+                      const float* fcs_mu, const float* fcs_rstd, const float* v_mu, void* out, int dtype, int B, int H,
+                      int Nc, int Ns, int activation, mhada_stream_t s_) {
   hipStream_t s = (hipStream_t)s_;
   if (!q || !kv || !fcs || !fcs_mu || !fcs_rstd || !v_mu || !out || B <= 0 || H <= 0 || Nc <= 0 || Ns <= 0)
-    return fail("mhada_attn: bad args");
-  if (!vt) return fail("mhada_attn: needs the transposed V' image (mhada_transpose_v)");
-  if (activation != MHADA_ACT_SOFTMAX && activation != MHADA_ACT_COSINE) return fail("mhada_attn: bad activation");
+    return fail(std::string(name) + ": bad args");
+  if (!vt) return fail(std::string(name) + ": needs the transposed V' image (mhada_transpose_v)");
+  if (activation != MHADA_ACT_SOFTMAX && activation != MHADA_ACT_COSINE) return fail(std::string(name) + ": bad activation");
+  if (SHARED && activation != MHADA_ACT_SOFTMAX) return fail(std::string(name) + ": softmax only");
+  if (SHARED && dtype != MHADA_F32 && dtype != MHADA_BF16) return fail(std::string(name) + ": bad dtype");
   AttnP p;
   p.q = q; p.kv = kv; p.vt = vt; p.fcs = fcs; p.fcs_mu = fcs_mu; p.fcs_rstd = fcs_rstd; p.v_mu = v_mu;
   p.out = out; p.B = B; p.H = H; p.Nc = Nc; p.Ns = Ns;
@@ -887,17 +916,31 @@ extern "C" int mhada_attn(const void* q, const void* kv, const void* vt, const f
   // blocks smaller than the CU count (B = 1 at 512^2: 128 blocks) leaves CUs idle, so it runs 4-wave
   // blocks there (one wave per SIMD instead of two, twice as many CUs covered)
   int nw = tuning().attn_waves;
-  if (nw == 0) nw = (long long)B * H * ((Nc + 255) / 256) < num_cus() ? 4 : 8;
+  if (nw == 0) nw = routed(B) * H * ((Nc + 255) / 256) < num_cus() ? 4 : 8;  // routed: common.h
   p.nqb = (Nc + 32 * nw - 1) / (32 * nw);
   const long long nblk = (long long)B * H * p.nqb;
-  if (nblk > (1LL << 31) - 1) return fail("mhada_attn: grid too large");
+  if (nblk > (1LL << 31) - 1) return fail(std::string(name) + ": grid too large");
   p.nblk = (int)nblk;
   if (nw == 8) {
-    launch_attn<8>(p, dtype, activation, s);
+    launch_attn<8, SHARED>(p, dtype, activation, s);
   } else {
-    launch_attn<4>(p, dtype, activation, s);
+    launch_attn<4, SHARED>(p, dtype, activation, s);
   }
-  return check_launch("mhada_attn");
+  return check_launch(name);
+}
+
+extern "C" int mhada_attn(const void* q, const void* kv, const void* vt, const float* fcs, const float* fcs_mu,
+                          const float* fcs_rstd, const float* v_mu, void* out, int dtype, int B, int H, int Nc,
+                          int Ns, int activation, mhada_stream_t s_) {
+  return attn_entry<false>("mhada_attn", q, kv, vt, fcs, fcs_mu, fcs_rstd, v_mu, out, dtype, B, H, Nc, Ns, activation,
+                           s_);
+}
+
+extern "C" int mhada_attn_shared(const void* q, const void* kv, const void* vt, const float* fcs, const float* fcs_mu,
+                                 const float* fcs_rstd, const float* v_mu, void* out, int dtype, int B, int H, int Nc,
+                                 int Ns, int activation, mhada_stream_t s_) {
+  return attn_entry<true>("mhada_attn_shared", q, kv, vt, fcs, fcs_mu, fcs_rstd, v_mu, out, dtype, B, H, Nc, Ns,
+                          activation, s_);
 }
 
 #ifdef ATTN_CLOCK

@@ -9,7 +9,7 @@ constexpr float kRescaleThr = 32.0f;  // log2 units: P <= 2^32, sums stay far be
 
 struct AttnP {
   const void* q;    // [B][H][Nc][64]
-  const void* kv;   // [B][H][Ns][128]
+  const void* kv;   // [B][H][Ns][128]; the shared-style kernels: one style's [H][Ns][128] (vt, v_mu likewise)
   const void* vt;   // bf16: [B][H][128][ldt], keys permuted within groups of 16
   const float* fcs; // [B][Nc][C]
   const float* fcs_mu;
@@ -25,6 +25,14 @@ struct AttnP {
   float* mo;
   float* lse;
 };
+
+// The shared-style kernel forms (mhada_attn_shared, mhada_attn_split3_shared, _planes_shared) are this flag
+// in an int template parameter the kernel already has, not a parameter of their own: attn_f32_kernel and
+// attn_bf16_kernel carry it in the activation (ACTF), attn_bf16_fs_kernel in the tile keys (TKF: <8, 384>),
+// attn_bf16_fsq_kernel in the wave count (NWF: <260>, <264>), attn_s3_kernel in the interleave (ILF: 257).  Each
+// kernel strips it first thing.  A parameter of its own would rename every existing instantiation; this way they
+// keep their mangled names (tools/isa_diff.py pairs kernels by name) and their code.
+constexpr int kAttnShared = 0x100;
 
 MHADA_DEV float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
 
@@ -134,7 +142,8 @@ MHADA_DEV void softmax_step(f32x16 (&S)[NKB], f32x16 (&O)[NO], float& m2, float&
 
 // Epilogue shared by both variants.  O[blk] holds O^T[dv][q] for dv = (r&3)+8(r>>2)+4h+32(blk&1);
 // blk 0,1: sum p v'   blk 2,3: sum p v'^2.
-template <typename T>
+// SHARED (the shared-style entries): v_mu is one style's [C] for every frame b.
+template <typename T, bool SHARED = false>
 MHADA_DEV void attn_epilogue(const AttnP& p, const f32x16 (&O)[4], float l, int b, int hh, int q, int h) {
   const int C = p.H * 64;
   const float lt = l + __shfl_xor(l, 32, 64);
@@ -143,7 +152,7 @@ MHADA_DEV void attn_epilogue(const AttnP& p, const f32x16 (&O)[4], float l, int 
   const float* fr = p.fcs + ((long long)b * p.Nc + q) * C + hh * 64;
   const float* mu = p.fcs_mu + (long long)b * C + hh * 64;
   const float* rs = p.fcs_rstd + (long long)b * C + hh * 64;
-  const float* vm = p.v_mu + (long long)b * C + hh * 64;
+  const float* vm = p.v_mu + (SHARED ? 0LL : (long long)b * C) + hh * 64;
   T* orow = reinterpret_cast<T*>(p.out) + ((long long)b * p.Nc + q) * C + hh * 64;
 #pragma unroll
   for (int blk = 0; blk < 2; ++blk) {
@@ -242,7 +251,8 @@ MHADA_DEV int fsq_key(int r, int t) { return 16 * (r >> 3) + 4 * ((r >> 2) & 1) 
 // dv = 16 dvb + 4g + e (dvb 0-3: sum p v', 4-7: sum p v'^2); lt = the full row sums.
 // PLANES (T = float): p.out is bf16 [3][B Nc][C], the fp32 result as its three round-to-nearest planes
 // (r0 = bf16(res), r1 = bf16(res - r0), r2 = bf16(res - r0 - r1): the SPLIT3 GEMM's A operand), no fp32 row.
-template <typename T, bool PLANES = false>
+// SHARED: as attn_epilogue's.
+template <typename T, bool PLANES = false, bool SHARED = false>
 MHADA_DEV void attn_epilogue_q(const AttnP& p, const f32x4 (&O)[2][8], const float (&lt)[2], int b, int hh, int q0,
                                int g, int r16) {
   const int C = p.H * 64;
@@ -254,7 +264,7 @@ MHADA_DEV void attn_epilogue_q(const AttnP& p, const f32x4 (&O)[2][8], const flo
     const float* fr = p.fcs + ((long long)b * p.Nc + q) * C + hh * 64;
     const float* mu = p.fcs_mu + (long long)b * C + hh * 64;
     const float* rs = p.fcs_rstd + (long long)b * C + hh * 64;
-    const float* vm = p.v_mu + (long long)b * C + hh * 64;
+    const float* vm = p.v_mu + (SHARED ? 0LL : (long long)b * C) + hh * 64;
     T* orow = reinterpret_cast<T*>(p.out) + ((long long)b * p.Nc + q) * C + hh * 64;
 #pragma unroll
     for (int dvb = 0; dvb < 4; ++dvb) {

@@ -396,8 +396,13 @@ MHADA_DEV void attn_train_epilogue_q(const AttnP& p, const f32x4 (&O)[2][8], con
 // interleave with the Q K^T of group 1 beside the split of group 0 measured no better).
 // PLANES (inference): the output as its three bf16 planes [3][B Nc][64 H] (attn_epilogue_q PLANES), the A
 // operand of the out_conv SPLIT3 GEMM, instead of fp32 rows.
-template <int NW, bool TRAIN = false, bool QK32 = false, int ACC = 0, int IL = 0, bool PLANES = false>
+// SHARED (ILF = IL | kAttnShared; mhada_attn_split3_shared / _planes_shared): the plane image and v_mu
+// belong to ONE style that every frame b attends to; everything else, and so every frame's bits, as the
+// per-batch form.
+template <int NW, bool TRAIN = false, bool QK32 = false, int ACC = 0, int ILF = 0, bool PLANES = false>
 __global__ void __launch_bounds__(64 * NW, 1) attn_s3_kernel(const AttnP p) {
+  constexpr int IL = ILF & ~kAttnShared;
+  constexpr bool SHARED = (ILF & kAttnShared) != 0;
   constexpr int TK = kS3Tk;
   constexpr int KPL = TK * 64, VPL = 128 * TK;                // bf16 elements per plane
   constexpr int KREG = QK32 ? 2 * TK * 64 : 3 * KPL;          // bf16 elements of the slot's K region
@@ -438,7 +443,7 @@ __global__ void __launch_bounds__(64 * NW, 1) attn_s3_kernel(const AttnP p) {
       }
     }
   }
-  const bf16* kp = reinterpret_cast<const bf16*>(p.kv) + bh * s3_image(ldt);
+  const bf16* kp = reinterpret_cast<const bf16*>(p.kv) + (SHARED ? hh : bh) * s3_image(ldt);
   const bf16* vp = kp + 192LL * ldt;
   // per-lane DMA sources: piece NW i + wave; K pieces hold 8 key rows of one plane, V pieces 8 rows
   int ksrc[KPW], vsrc[VPW];
@@ -670,7 +675,7 @@ __global__ void __launch_bounds__(64 * NW, 1) attn_s3_kernel(const AttnP p) {
   }
   if (__any(!(lt[0] <= kShiftSumThr) || !(lt[1] <= kShiftSumThr))) attn_exact_q3<QK32>(p, kp, vp, qf, qreg, O, lt, mx, g, r16);
   if constexpr (TRAIN) attn_train_epilogue_q(p, O, lt, mx, bh, q0, g, r16);
-  else attn_epilogue_q<float, PLANES>(p, O, lt, b, hh, q0, g, r16);
+  else attn_epilogue_q<float, PLANES, SHARED>(p, O, lt, b, hh, q0, g, r16);
 }
 
 }  // namespace mhada
@@ -700,7 +705,7 @@ extern "C" int mhada_kv_proj_split3(const float* fs, const float* mu_s, const fl
 
 static int attn_split3_launch(const char* name, const float* q, const void* img, const float* fcs, const float* fcs_mu,
                               const float* fcs_rstd, const float* v_mu, void* out, bool planes, int B, int H, int Nc,
-                              int Ns, mhada_stream_t s_) {
+                              int Ns, mhada_stream_t s_, bool shared = false) {
   if (!q || !img || !fcs || !fcs_mu || !fcs_rstd || !v_mu || !out || B <= 0 || H <= 0 || Nc <= 0 || Ns <= 0)
     return fail(std::string(name) + ": bad args");
   AttnP p = {};
@@ -711,18 +716,27 @@ static int attn_split3_launch(const char* name, const float* q, const void* img,
   // waves per block as mhada_attn: tuning attn_waves, 0 = 8, or 4 when the 8-wave grid has fewer
   // blocks than CUs
   int nw = tuning().attn_waves;
-  if (nw == 0) nw = (long long)B * H * ((Nc + 255) / 256) < num_cus() ? 4 : 8;
+  if (nw == 0) nw = routed(B) * H * ((Nc + 255) / 256) < num_cus() ? 4 : 8;  // routed: common.h
   p.nqb = (Nc + 32 * nw - 1) / (32 * nw);
   const long long nblk = (long long)B * H * p.nqb;
   if (nblk > (1LL << 31) - 1) return fail(std::string(name) + ": grid too large");
   p.nblk = (int)nblk;
   const hipStream_t s = (hipStream_t)s_;
-  if (planes) {
-    if (nw == 8) hipLaunchKernelGGL((attn_s3_kernel<8, false, false, 0, 1, true>), dim3(p.nblk), dim3(512), 0, s, p);
-    else hipLaunchKernelGGL((attn_s3_kernel<4, false, false, 0, 1, true>), dim3(p.nblk), dim3(256), 0, s, p);
+  const dim3 grid(p.nblk), blk(64 * nw);
+  if (shared) {  // same waves-per-block rule, so each frame runs the form it would run through the per-batch entry
+    if (planes) {
+      if (nw == 8) hipLaunchKernelGGL((attn_s3_kernel<8, false, false, 0, 1 | kAttnShared, true>), grid, blk, 0, s, p);
+      else hipLaunchKernelGGL((attn_s3_kernel<4, false, false, 0, 1 | kAttnShared, true>), grid, blk, 0, s, p);
+    } else {
+      if (nw == 8) hipLaunchKernelGGL((attn_s3_kernel<8, false, false, 0, 1 | kAttnShared>), grid, blk, 0, s, p);
+      else hipLaunchKernelGGL((attn_s3_kernel<4, false, false, 0, 1 | kAttnShared>), grid, blk, 0, s, p);
+    }
+  } else if (planes) {
+    if (nw == 8) hipLaunchKernelGGL((attn_s3_kernel<8, false, false, 0, 1, true>), grid, blk, 0, s, p);
+    else hipLaunchKernelGGL((attn_s3_kernel<4, false, false, 0, 1, true>), grid, blk, 0, s, p);
   } else {
-    if (nw == 8) hipLaunchKernelGGL((attn_s3_kernel<8, false, false, 0, 1>), dim3(p.nblk), dim3(512), 0, s, p);
-    else hipLaunchKernelGGL((attn_s3_kernel<4, false, false, 0, 1>), dim3(p.nblk), dim3(256), 0, s, p);
+    if (nw == 8) hipLaunchKernelGGL((attn_s3_kernel<8, false, false, 0, 1>), grid, blk, 0, s, p);
+    else hipLaunchKernelGGL((attn_s3_kernel<4, false, false, 0, 1>), grid, blk, 0, s, p);
   }
   return check_launch(name);
 }
@@ -738,6 +752,21 @@ extern "C" int mhada_attn_split3_planes(const float* q, const void* img, const f
                                         int Ns, mhada_stream_t s_) {
   return attn_split3_launch("mhada_attn_split3_planes", q, img, fcs, fcs_mu, fcs_rstd, v_mu, planes, true, B, H, Nc, Ns,
                             s_);
+}
+
+// The shared-style forms: img is ONE style's [H][576 ldt], v_mu its [64H]; q, fcs and the statistics per frame.
+extern "C" int mhada_attn_split3_shared(const float* q, const void* img, const float* fcs, const float* fcs_mu,
+                                        const float* fcs_rstd, const float* v_mu, float* out, int B, int H, int Nc,
+                                        int Ns, mhada_stream_t s_) {
+  return attn_split3_launch("mhada_attn_split3_shared", q, img, fcs, fcs_mu, fcs_rstd, v_mu, out, false, B, H, Nc, Ns, s_,
+                            true);
+}
+
+extern "C" int mhada_attn_split3_planes_shared(const float* q, const void* img, const float* fcs, const float* fcs_mu,
+                                               const float* fcs_rstd, const float* v_mu, void* planes, int B, int H,
+                                               int Nc, int Ns, mhada_stream_t s_) {
+  return attn_split3_launch("mhada_attn_split3_planes_shared", q, img, fcs, fcs_mu, fcs_rstd, v_mu, planes, true, B, H,
+                            Nc, Ns, s_, true);
 }
 
 // Training forward as SPLIT3 products (the contract of mhada_attn_train_fwd_vt, attn.hip): q, x

@@ -190,6 +190,12 @@ inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 // compute units of the current device (abi.hip): queried once per process, 256 if the query fails
 int num_cus();
 
+// Form routing for chunked calls (abi.hip, mhada_set_route): the dispatch rules that choose a kernel form from
+// the rows or the batch of a call (the fp32 GEMM's tile-fill rule, the attention's waves per block) evaluate
+// routed(x) = x * mul / div, so that a chunk of div frames takes the forms a whole clip of mul frames takes
+// and a frame's bits do not depend on the chunking.  Off (mul = div = 0, the default): routed(x) = x.
+long long routed(long long x);
+
 // Bijective XCD-aware block remap (cdna_hip_programming.md §5 "XCD swizzle must be
 // bijective"): blocks b, b+8, b+16 ... are dealt to one XCD; give each XCD a contiguous
 // range of logical ids so neighbouring tiles (which share operands) share its L2.

@@ -2002,7 +2002,7 @@ static int dispatch_tile(const GemmP& p, int nz, hipStream_t s) {
     // that the 128x128 kernel keeps more of the chip busy; the 1080p frame's N = 512 GEMMs have
     // 254 tiles); tuning gemm_pp / gemm_persist = 0 disable
     if constexpr (sizeof(TA) == 4 && (AMODE == MHADA_A_ROWS || AMODE == MHADA_A_CONV3X3 || AMODE == MHADA_A_CONV3X3_ZERO)) {
-      const long long t256 = (long long)((p.M + 255) / 256) * ((p.N + 255) / 256) * nz;
+      const long long t256 = ((routed(p.M) + 255) / 256) * ((p.N + 255) / 256) * nz;  // routed: common.h
       if (p.N > 128 && p.K % 32 == 0 && p.K >= 64 && 8 * t256 >= 7LL * num_cus() && pp_enabled() && persist_enabled() &&
           pp_offsets_fit(p, AMODE)) {
         return launch_gemm_pp<float, TO, AMODE>(p, nz, s);

@@ -1131,6 +1131,45 @@ extern "C" int mhada_vit_batch_attn_half2(const float* qkv, void* planes, long l
   return check_launch("mhada_vit_batch_attn_half2");
 }
 
+// The grouped forms: the L images are `groups` independent calls of L / groups images each, in one launch.
+// Built for L / groups == 1 (one image per call, the clip route): a token then attends to itself alone, so
+// the groups' tokens are one call of L * ntok tokens with a batch axis of 1: these entries are the entries
+// above at L = 1 (the pass-through of V, or its planes) over L * ntok tokens, nothing more.
+static int grouped_shape(const char* name, int L, int ntok, int groups, int& tok) {
+  if (L <= 0 || groups <= 0 || L % groups) return fail(std::string(name) + ": L must be a positive multiple of groups");
+  if (L != groups) return fail(std::string(name) + ": only L / groups == 1 is built");
+  if (ntok < 0 || (long long)L * ntok > (1LL << 31) - 1) return fail(std::string(name) + ": bad ntok");
+  tok = L * ntok;
+  return MHADA_OK;
+}
+// an error of the delegated call, under the name the caller used
+static int grouped_rc(const char* name, int rc) {
+  if (rc != MHADA_OK) set_error(std::string(name) + ": " + mhada_last_error());
+  return rc;
+}
+
+extern "C" int mhada_vit_batch_attn_grouped(const void* qkv, void* out, int dtype, int L, int ntok, int heads,
+                                            int head_dim, int groups, mhada_stream_t s_) {
+  int tok;
+  if (int rc = grouped_shape("mhada_vit_batch_attn_grouped", L, ntok, groups, tok)) return rc;
+  return grouped_rc("mhada_vit_batch_attn_grouped", mhada_vit_batch_attn(qkv, out, dtype, 1, tok, heads, head_dim, s_));
+}
+
+extern "C" int mhada_vit_batch_attn_split3_grouped(const float* qkv, void* planes, long long pstride, int L, int ntok,
+                                                   int heads, int head_dim, int groups, mhada_stream_t s_) {
+  int tok;
+  if (int rc = grouped_shape("mhada_vit_batch_attn_split3_grouped", L, ntok, groups, tok)) return rc;
+  return grouped_rc("mhada_vit_batch_attn_split3_grouped", mhada_vit_batch_attn_split3(qkv, planes, pstride, 1, tok, heads, head_dim, s_));
+}
+
+extern "C" int mhada_vit_batch_attn_half2_grouped(const float* qkv, void* planes, long long pstride,
+                                                  const float* out_scale, int L, int ntok, int heads, int head_dim,
+                                                  int groups, mhada_stream_t s_) {
+  int tok;
+  if (int rc = grouped_shape("mhada_vit_batch_attn_half2_grouped", L, ntok, groups, tok)) return rc;
+  return grouped_rc("mhada_vit_batch_attn_half2_grouped", mhada_vit_batch_attn_half2(qkv, planes, pstride, out_scale, 1, tok, heads, head_dim, s_));
+}
+
 extern "C" int mhada_pos_embed(const float* pos, float* out, int C, int bh, int bw, int oh, int ow,
                                mhada_stream_t s_) {
   if (!pos || !out || C <= 0 || bh <= 0 || bw <= 0 || oh <= 0 || ow <= 0) return fail("mhada_pos_embed: bad args");

@@ -155,6 +155,14 @@ SIGNATURES = {
     "mhada_hist_u8": (_I, [_vp, _I, _I, _I, _c_ll, _I, _vp, _vp]),
     "mhada_lpips_layer_work": (_c_ll, [_I, _c_ll, _I]),
     "mhada_lpips_layer": (_I, [_vp, _vp, _vp, _I, _c_ll, _I, _vp, _c_ll, _vp, _vp]),
+    # clips: B frames against one style, and the grouped batch-axis attention
+    "mhada_attn_shared": (_I, [_vp] * 8 + [_I, _I, _I, _I, _I, _I, _vp]),
+    "mhada_attn_split3_shared": (_I, [_vp] * 7 + [_I, _I, _I, _I, _vp]),
+    "mhada_attn_split3_planes_shared": (_I, [_vp] * 7 + [_I, _I, _I, _I, _vp]),
+    "mhada_set_route": (_I, [_I, _I]),
+    "mhada_vit_batch_attn_grouped": (_I, [_vp, _vp, _I, _I, _I, _I, _I, _I, _vp]),
+    "mhada_vit_batch_attn_split3_grouped": (_I, [_vp, _vp, _c_ll, _I, _I, _I, _I, _I, _vp]),
+    "mhada_vit_batch_attn_half2_grouped": (_I, [_vp, _vp, _c_ll, _vp, _I, _I, _I, _I, _I, _vp]),
 }
 
 _lib = None

@@ -162,7 +162,7 @@ def _split3_fills(M: int, N: int, dev: torch.device) -> bool:
     idx = dev.index if dev.index is not None else torch.cuda.current_device()
     if idx not in _NUM_CUS:
         _NUM_CUS[idx] = torch.cuda.get_device_properties(idx).multi_processor_count
-    return 8 * ((M + 255) // 256) * ((N + 255) // 256) >= 7 * _NUM_CUS[idx]
+    return 8 * ((ops.routed(M) + 255) // 256) * ((N + 255) // 256) >= 7 * _NUM_CUS[idx]
 
 
 def _w6(L: dict, key: str) -> torch.Tensor:
@@ -207,8 +207,25 @@ def _h2_chain(L: dict, key: str) -> Optional[dict]:
     return L[k2]
 
 
-def vit_forward(vit, x: torch.Tensor) -> List[torch.Tensor]:
-    """VisionTransformer.forward (vit.py:148-169) on the HIP path."""
+def vit_forward(vit, x: torch.Tensor, groups: int = 1) -> List[torch.Tensor]:
+    """VisionTransformer.forward (vit.py:148-169) on the HIP path.
+
+    ``groups`` > 1: x is that many calls' batches concatenated, and every result equals that call's own.
+    The reference attends over the batch axis (vit.py:48,59), so without it the images of one call mix;
+    everything else in the ViT is per token.  Built for one image per group (the frames of a clip,
+    ``VideoStylizer.stylize_clip``): the batch-axis attention is then the grouped pass-through of V
+    (mhada_vit_batch_attn*_grouped, one launch).  A CPU tensor evaluates the groups one by one
+    (autograd_path.vit_forward)."""
+    if groups != 1:
+        if groups < 1 or x.dim() != 4 or x.shape[0] % groups:
+            raise ValueError(f"groups must divide the batch, got groups {groups} for {tuple(x.shape)}")
+        if not x.is_cuda:
+            from . import autograd_path
+            with torch.no_grad():
+                return autograd_path.vit_forward(vit, x, groups)
+        if x.shape[0] != groups:
+            raise ValueError("vit_forward(groups=) is built for one image per group on the device, got "
+                             f"{x.shape[0] // groups}")
     require_device(x, "VisionTransformer")
     dt = resolve_compute_dtype(vit)
     prep = vit_prep(vit, dt)
@@ -247,16 +264,21 @@ def vit_forward(vit, x: torch.Tensor) -> List[torch.Tensor]:
             hb = ops.layernorm(xs, L["ln1_g"], L["ln1_b"], dt, L["eps"])
             qkv = ops.linear(hb, L["w_qkv"], L["b_qkv"], dt)
         # the out-projection as a SPLIT3 GEMM too: the batch-axis attention writes the planes (no fp32 att)
-        if split_mlp and ops.F32_SPLIT_OUTPROJ and C == L["heads"] * HEAD_DIM and B <= ops.VIT_ATTN_SPLIT3_MAX_L:
+        q3 = qkv.view(B, N, 3 * C)
+        if split_mlp and ops.F32_SPLIT_OUTPROJ and C == L["heads"] * HEAD_DIM \
+                and B // groups <= ops.VIT_ATTN_SPLIT3_MAX_L:
             h2o = _h2_chain(L, "w_o")
             if h2o is not None:  # the attention output is bounded by V's bound: fp16 planes, HALF2 GEMM
-                att2 = ops.vit_batch_attn_half2(qkv.view(B, N, 3 * C), B, N, L["heads"], h2o["u"])
+                att2 = ops.vit_batch_attn_half2(q3, B, N, L["heads"], h2o["u"]) if groups == 1 else \
+                    ops.vit_batch_attn_half2_grouped(q3, B, N, L["heads"], h2o["u"], groups)
                 xs = ops.linear_half2_planes(att2, h2o["w2"], h2o["cs"], L["b_o"], residual=xs)
             else:
-                att3 = ops.vit_batch_attn_split3(qkv.view(B, N, 3 * C), B, N, L["heads"])
+                att3 = ops.vit_batch_attn_split3(q3, B, N, L["heads"]) if groups == 1 else \
+                    ops.vit_batch_attn_split3_grouped(q3, B, N, L["heads"], groups)
                 xs = ops.linear_split3(att3, _w6(L, "w_o"), L["b_o"], torch.float32, residual=xs)
         else:
-            att = ops.vit_batch_attn(qkv.view(B, N, 3 * C), B, N, L["heads"])
+            att = ops.vit_batch_attn(q3, B, N, L["heads"]) if groups == 1 else \
+                ops.vit_batch_attn_grouped(q3, B, N, L["heads"], groups)
             xs = ops.linear(att.view(B * N, C), L["w_o"], L["b_o"], torch.float32, residual=xs)
         if split_mlp:  # MLP1 writes its ReLU output as planes, MLP2 consumes them (SPLIT3; HALF2 where prepared)
             h2c = _h2_chain(L, "w2")  # None wherever h2m is
@@ -328,7 +350,13 @@ def block_forward(blk, fc: _Feat, fs: Optional[_Feat], fcs: _Feat, dt: torch.dty
     its V'^T image): when it is filled they are reused (fs may then be None), when it is an empty
     dict they are computed and stored into it (the per-style cache of adaformer_forward).
     ``want_bf16``: the out_conv GEMM also writes a bf16 copy of the block output (``.t16``) for
-    the decoder's first conv (the last block of a bf16 forward)."""
+    the decoder's first conv (the last block of a bf16 forward).
+
+    One style for B > 1 content frames (a style batch of 1, in ``fs`` or in the cache; the clip route of
+    ``VideoStylizer.stylize_clip``): softmax at head width 64 takes the shared-style entries
+    (mhada_attn_shared / attn_split3_shared / attn_split3_planes_shared; the fold is fold_block's), so the
+    style-side tensors exist once; every frame gets the result of its own B = 1 call.  Other
+    combinations of unequal batches raise, as before."""
     if blk.head_dim in ops.HD_WIDTHS:
         return _block_forward_hd(blk, fc, fs, fcs, dt, side, want_bf16)
     if blk.head_dim != HEAD_DIM:
@@ -346,18 +374,23 @@ def block_forward(blk, fc: _Feat, fs: Optional[_Feat], fcs: _Feat, dt: torch.dty
     if cached:
         mu_s, rstd_s, mom, Ns = side["mu_s"], side["rstd_s"], side.get("mom"), side["Ns"]
         kv, vt, img = side.get("kv"), side.get("vt"), side.get("img")
-        if side["B"] != B:
-            raise ValueError(f"cached style batch {side['B']} != content batch {B}")
+        Bs = side["B"]
     else:
         if fs.t.shape[2] != C:
             raise ValueError(f"channel mismatch: block expects {C}")
         mu_s, rstd_s = fs.stats()
+        Bs = fs.t.shape[0]
+    shared = Bs == 1 and B > 1 and act == ACT_SOFTMAX  # one style, B frames
+    if Bs != B and not shared:
+        raise ValueError(f"cached style batch {Bs} != content batch {B}" if cached else
+                         f"style batch {Bs} != content batch {B}")
     if Cc != C or fcs.t.shape[2] != C:
         raise ValueError(f"channel mismatch: block expects {C}")
     mu_c, rstd_c = fc.stats()
     mu_o, rstd_o = fcs.stats()
-    wq, wkv, bkv, v_mu = ops.fold_block(prep["wf"], prep["wg"], prep["wh"], prep["bg"], prep["bh"],
-                                        rstd_c, mu_s, rstd_s, dt, ops.LOG2E if act == ACT_SOFTMAX else 1.0)
+    fold = ops.fold_block_shared if shared else ops.fold_block
+    wq, wkv, bkv, v_mu = fold(prep["wf"], prep["wg"], prep["wh"], prep["bg"], prep["bh"],
+                              rstd_c, mu_s, rstd_s, dt, ops.LOG2E if act == ACT_SOFTMAX else 1.0)
     dev = fc.t.device
     q = torch.empty(B, H, Nc, HEAD_DIM, device=dev, dtype=dt)
     ops.gemm(a=fc.t, w=wq, c=q, M=Nc, N=HEAD_DIM, K=HEAD_DIM, compute=dt, lda=C, sa=(Nc * C, HEAD_DIM),
@@ -368,16 +401,16 @@ def block_forward(blk, fc: _Feat, fs: Optional[_Feat], fcs: _Feat, dt: torch.dty
         # K|V' projection written straight as the SPLIT3 attention's bf16 plane image (no fp32 kv / vt)
         img = ops.kv_proj_split3(fs.t, mu_s, wkv, bkv)
         if side is not None:
-            side.update(mu_s=mu_s, rstd_s=rstd_s, img=img, Ns=Ns, B=B)
+            side.update(mu_s=mu_s, rstd_s=rstd_s, img=img, Ns=Ns, B=Bs)
     elif not cached:
         Ns = fs.t.shape[1]
         # K|V' projection: K rows into kv[..., :64] (the attention's K operand), V' straight into
         # the transposed V'^T | V'^2^T image vt (the GEMM's vt epilogue; kv[..., 64:] unused)
-        kv = torch.empty(B, H, Ns, 2 * HEAD_DIM, device=dev, dtype=dt)
+        kv = torch.empty(Bs, H, Ns, 2 * HEAD_DIM, device=dev, dtype=dt)
         ldt = (Ns + 63) // 64 * 64
-        vt = torch.empty(B, H, 2 * HEAD_DIM, ldt, device=dev, dtype=dt)
+        vt = torch.empty(Bs, H, 2 * HEAD_DIM, ldt, device=dev, dtype=dt)
         ops.gemm(a=fs.t, w=wkv, c=kv, M=Ns, N=2 * HEAD_DIM, K=HEAD_DIM, compute=dt, lda=C, sa=(Ns * C, HEAD_DIM),
-                 nb=(B, H), a_mu=mu_s, smu=(C, HEAD_DIM), ldw=HEAD_DIM,
+                 nb=(Bs, H), a_mu=mu_s, smu=(C, HEAD_DIM), ldw=HEAD_DIM,
                  sw=(H * 2 * HEAD_DIM * HEAD_DIM, 2 * HEAD_DIM * HEAD_DIM), bias=bkv, sb=(0, 2 * HEAD_DIM),
                  ldc=2 * HEAD_DIM, sc=(H * Ns * 2 * HEAD_DIM, Ns * 2 * HEAD_DIM),
                  vt=vt, ldt=ldt, svt=(H * 2 * HEAD_DIM * ldt, 2 * HEAD_DIM * ldt))
@@ -386,7 +419,7 @@ def block_forward(blk, fc: _Feat, fs: Optional[_Feat], fcs: _Feat, dt: torch.dty
             ops.cosine_prep(None, kv)
             mom = ops.cosine_moments(kv, vt)
         if side is not None:
-            side.update(mu_s=mu_s, rstd_s=rstd_s, kv=kv, vt=vt, mom=mom, Ns=Ns, B=B)
+            side.update(mu_s=mu_s, rstd_s=rstd_s, kv=kv, vt=vt, mom=mom, Ns=Ns, B=Bs)
     if act == ACT_COSINE:
         ops.cosine_prep(q, None)
         with _timed("mhada_attn"):
@@ -394,7 +427,8 @@ def block_forward(blk, fc: _Feat, fs: Optional[_Feat], fcs: _Feat, dt: torch.dty
     elif split_attn and ops.F32_SPLIT_OUTPROJ and _split3_fills(B * Nc, C, dev):
         # the attention writes its output as bf16 planes and out_conv runs as a SPLIT3 GEMM (no fp32 att)
         with _timed("mhada_attn"):
-            att3 = ops.attn_split3_planes(q, img, Ns, fcs.t, mu_o, rstd_o, v_mu)  # [3][B Nc][C] bf16
+            att3 = (ops.attn_split3_planes_shared if shared else ops.attn_split3_planes)(
+                q, img, Ns, fcs.t, mu_o, rstd_o, v_mu)  # [3][B Nc][C] bf16
         if "w_out_split3" not in prep:
             with torch.no_grad():
                 prep["w_out_split3"] = ops.split3_weight(prep["w_out"])
@@ -402,10 +436,12 @@ def block_forward(blk, fc: _Feat, fs: Optional[_Feat], fcs: _Feat, dt: torch.dty
         return _Feat(out.view(B, Nc, C), fc.h, fc.w)
     elif split_attn:
         with _timed("mhada_attn"):
-            att = ops.attn_split3(q, img, Ns, fcs.t, mu_o, rstd_o, v_mu)  # [B][Nc][C] fp32
+            att = (ops.attn_split3_shared if shared else ops.attn_split3)(
+                q, img, Ns, fcs.t, mu_o, rstd_o, v_mu)  # [B][Nc][C] fp32
     else:
         with _timed("mhada_attn"):
-            att = ops.mhada_attn(q, kv, vt, fcs.t, mu_o, rstd_o, v_mu, act)  # [B][Nc][C] dt
+            att = ops.mhada_attn_shared(q, kv, vt, fcs.t, mu_o, rstd_o, v_mu) if shared else \
+                ops.mhada_attn(q, kv, vt, fcs.t, mu_o, rstd_o, v_mu, act)  # [B][Nc][C] dt
     out = torch.empty(B * Nc, C, device=dev, dtype=torch.float32)
     t16 = torch.empty(B * Nc, C, device=dev, dtype=torch.bfloat16) if want_bf16 else None
     ops.gemm(a=att.view(B * Nc, C), w=prep["w_out"], c=out, M=B * Nc, N=C, K=C, compute=dt, lda=C, ldw=C,

@@ -734,6 +734,60 @@ def vit_batch_attn_half2(qkv: torch.Tensor, L: int, ntok: int, heads: int, out_s
     return planes
 
 
+def _one_per_group(what: str, L: int, groups: int) -> None:
+    if groups < 1 or L % groups:
+        raise ValueError(f"{what}: L must be a positive multiple of groups")
+    if L != groups:
+        raise ValueError(f"{what}: only L / groups == 1 (one image per group) is built; "
+                         "vit_batch_attn(groups=) loops over any grouping")
+
+
+def vit_batch_attn_grouped(qkv: torch.Tensor, L: int, ntok: int, heads: int, groups: int) -> torch.Tensor:
+    """``mhada_vit_batch_attn_grouped``: ``vit_batch_attn`` with the L images of qkv [L][ntok][3C] taken as
+    ``groups`` independent calls, in ONE launch (the group comes from the grid); bit-identical to
+    ``vit_batch_attn`` on each group's slice.  Built for L / groups == 1 (the clip route): the output is V."""
+    _need_gpu(qkv)
+    _one_per_group("vit_batch_attn_grouped", L, groups)
+    if not qkv.is_contiguous():
+        raise ValueError("vit_batch_attn_grouped needs contiguous qkv")
+    C = qkv.shape[-1] // 3
+    out = torch.empty(L, ntok, C, device=qkv.device, dtype=qkv.dtype)
+    _call("mhada_vit_batch_attn_grouped", qkv, qkv.data_ptr(), out.data_ptr(), dt_code(qkv.dtype), L, ntok, heads,
+          C // heads, groups)
+    return out
+
+
+def vit_batch_attn_split3_grouped(qkv: torch.Tensor, L: int, ntok: int, heads: int, groups: int) -> torch.Tensor:
+    """``mhada_vit_batch_attn_split3_grouped``: the grouped form of ``vit_batch_attn_split3`` (planes
+    [3][L * ntok][C]); L / groups == 1, head_dim 64."""
+    _need_gpu(qkv)
+    _one_per_group("vit_batch_attn_split3_grouped", L, groups)
+    if qkv.dtype != torch.float32 or not qkv.is_contiguous():
+        raise ValueError("vit_batch_attn_split3_grouped needs contiguous float32 qkv")
+    C = qkv.shape[-1] // 3
+    planes = torch.empty(3, L * ntok, C, device=qkv.device, dtype=torch.bfloat16)
+    _call("mhada_vit_batch_attn_split3_grouped", qkv, qkv.data_ptr(), planes.data_ptr(), L * ntok * C, L, ntok,
+          heads, C // heads, groups)
+    return planes
+
+
+def vit_batch_attn_half2_grouped(qkv: torch.Tensor, L: int, ntok: int, heads: int, out_scale: torch.Tensor,
+                                 groups: int) -> torch.Tensor:
+    """``mhada_vit_batch_attn_half2_grouped``: the grouped form of ``vit_batch_attn_half2`` (fp16 planes
+    [2][L * ntok][C]); L / groups == 1, head_dim 64."""
+    _need_gpu(qkv, out_scale)
+    _one_per_group("vit_batch_attn_half2_grouped", L, groups)
+    C = qkv.shape[-1] // 3
+    if qkv.dtype != torch.float32 or not qkv.is_contiguous():
+        raise ValueError("vit_batch_attn_half2_grouped needs contiguous float32 qkv")
+    if out_scale.dtype != torch.float32 or out_scale.numel() != C or not out_scale.is_contiguous():
+        raise ValueError("vit_batch_attn_half2_grouped: out_scale must be contiguous float32 [C]")
+    planes = torch.empty(2, L * ntok, C, device=qkv.device, dtype=torch.float16)
+    _call("mhada_vit_batch_attn_half2_grouped", qkv, qkv.data_ptr(), planes.data_ptr(), L * ntok * C,
+          out_scale.data_ptr(), L, ntok, heads, C // heads, groups)
+    return planes
+
+
 def pos_embed(pos: torch.Tensor, oh: int, ow: int) -> torch.Tensor:
     _need_gpu(pos)
     _, C, bh, bw = pos.shape
@@ -836,6 +890,32 @@ def layernorm_bwd(x: torch.Tensor, dy: torch.Tensor, st: torch.Tensor, gamma: to
     return dx, dg, db
 
 
+_ROUTE = (0, 0)
+
+
+def routed(x: int) -> int:
+    """x as the form-routing rules count it: x * mul / div inside ``route_as``, else x."""
+    mul, div = _ROUTE
+    return x * mul // div if div else x
+
+
+@contextlib.contextmanager
+def route_as(mul: int, div: int):
+    """Within the block, every rule that chooses a kernel form from the rows or the batch of a call — here
+    (``engine._split3_fills``, ``instnorm_stats``' splits) and in the library (``mhada_set_route``: the fp32
+    GEMM's tile-fill rule, the attention's waves per block) — evaluates them times mul / div: a chunk of
+    ``div`` frames then takes the forms a clip of ``mul`` frames takes (``VideoStylizer.stylize_clip``)."""
+    global _ROUTE
+    saved = _ROUTE
+    _ROUTE = (mul, div)
+    _lib.check(_lib.load().mhada_set_route(mul, div), "mhada_set_route")
+    try:
+        yield
+    finally:
+        _ROUTE = saved
+        _lib.check(_lib.load().mhada_set_route(*saved), "mhada_set_route")
+
+
 def instnorm_stats(x: torch.Tensor, eps: float = 1e-5):
     """x [B][N][C] fp32 -> (mu, rstd) [B][C] fp32."""
     _need_gpu(x)
@@ -843,7 +923,7 @@ def instnorm_stats(x: torch.Tensor, eps: float = 1e-5):
         raise ValueError(f"instnorm_stats needs contiguous float32 token rows [B][N][C], got {x.dtype} "
                          f"{tuple(x.shape)}")
     B, N, C = x.shape
-    splits = max(1, min(N // 32, 2048 // max(1, B * ((C + 63) // 64))))
+    splits = max(1, min(N // 32, 2048 // max(1, routed(B) * ((C + 63) // 64))))
     mu = torch.empty(B, C, device=x.device, dtype=torch.float32)
     rstd = torch.empty(B, C, device=x.device, dtype=torch.float32)
     work = torch.empty(splits, B, C, 2, device=x.device, dtype=torch.float64)
@@ -870,6 +950,18 @@ def fold_block(wf, wg, wh, bg, bh, rstd_c, mu_s, rstd_s, dtype: torch.dtype, ksc
           rstd_c.data_ptr(), mu_s.data_ptr(), rstd_s.data_ptr(), wq.data_ptr(), wkv.data_ptr(), bkv.data_ptr(),
           v_mu.data_ptr(), kscale, dt_code(dtype), B, H)
     return wq, wkv, bkv, v_mu
+
+
+def fold_block_shared(wf, wg, wh, bg, bh, rstd_c, mu_s, rstd_s, dtype: torch.dtype, kscale: float = LOG2E):
+    """``fold_block`` for B content frames (rstd_c [B][C]) against ONE style (mu_s, rstd_s [1][C]): wq
+    [B][H][64][64] per frame; wkv [1][H][128][64], bkv and v_mu [1][C] of the style.  The existing entry with
+    the style statistics repeated (B x C floats): no kernel of its own, so the bits are fold_block's."""
+    B, C = rstd_c.shape
+    if mu_s.shape != (1, C) or rstd_s.shape != (1, C):
+        raise ValueError(f"fold_block_shared: the style statistics must be [1][{C}], got {tuple(mu_s.shape)}")
+    wq, wkv, bkv, v_mu = fold_block(wf, wg, wh, bg, bh, rstd_c, mu_s.expand(B, C).contiguous(),
+                                    rstd_s.expand(B, C).contiguous(), dtype, kscale)
+    return wq, wkv[:1], bkv, v_mu[:1]
 
 
 def transpose_v(kv: torch.Tensor) -> torch.Tensor:
@@ -928,6 +1020,38 @@ def mhada_attn(q, kv, vt, fcs, fcs_mu, fcs_rstd, v_mu, activation: int) -> torch
     _call("mhada_attn", q, q.data_ptr(), kv.data_ptr(), _ptr(vt), fcs.data_ptr(), fcs_mu.data_ptr(),
                                 fcs_rstd.data_ptr(), v_mu.data_ptr(), out.data_ptr(), dt_code(q.dtype), B, H, Nc,
                                 Ns, activation)
+    return out
+
+
+def _shared_style(what: str, q, fcs, fcs_mu, fcs_rstd, v_mu) -> None:
+    B, H, Nc, D = q.shape
+    C = H * 64
+    if D != 64 or not q.is_contiguous() or fcs.shape != (B, Nc, C) or fcs_mu.shape != (B, C) \
+            or fcs_rstd.shape != (B, C) or v_mu.shape != (1, C):
+        raise ValueError(f"{what}: needs q [B][H][Nc][64], fcs [B][Nc][{C}], per-frame statistics [B][{C}] and "
+                         f"one style's v_mu [1][{C}]; got q {tuple(q.shape)}, fcs {tuple(fcs.shape)}, "
+                         f"v_mu {tuple(v_mu.shape)}")
+    for t in (fcs, fcs_mu, fcs_rstd, v_mu):
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError(f"{what}: fcs, its statistics and v_mu must be contiguous float32")
+
+
+def mhada_attn_shared(q, kv, vt, fcs, fcs_mu, fcs_rstd, v_mu) -> torch.Tensor:
+    """``mhada_attn_shared``: the softmax ``mhada_attn`` of B frames (q [B][H][Nc][64], fcs and statistics
+    per frame) against ONE style (kv [1][H][Ns][128], vt [1][H][128][ceil64(Ns)], v_mu [1][C]); every frame
+    gets the bits of ``mhada_attn`` with the style operands repeated B times.  fp32 or bf16."""
+    _need_gpu(q, kv, vt, fcs, fcs_mu, fcs_rstd, v_mu)
+    _shared_style("mhada_attn_shared", q, fcs, fcs_mu, fcs_rstd, v_mu)
+    B, H, Nc, _ = q.shape
+    Ns = kv.shape[2]
+    ldt = (Ns + 63) // 64 * 64
+    if kv.shape != (1, H, Ns, 128) or vt.shape != (1, H, 128, ldt) or kv.dtype != q.dtype or vt.dtype != q.dtype \
+            or not kv.is_contiguous() or not vt.is_contiguous():
+        raise ValueError(f"mhada_attn_shared: kv / vt must be one style's contiguous [1][{H}][Ns][128] / "
+                         f"[1][{H}][128][{ldt}] of q's dtype, got {tuple(kv.shape)} / {tuple(vt.shape)}")
+    out = torch.empty(B, Nc, H * 64, device=q.device, dtype=q.dtype)
+    _call("mhada_attn_shared", q, q.data_ptr(), kv.data_ptr(), vt.data_ptr(), fcs.data_ptr(), fcs_mu.data_ptr(),
+          fcs_rstd.data_ptr(), v_mu.data_ptr(), out.data_ptr(), dt_code(q.dtype), B, H, Nc, Ns, _lib.ACT_SOFTMAX)
     return out
 
 
@@ -1113,6 +1237,41 @@ def attn_split3_planes(q, img, Ns: int, fcs, fcs_mu, fcs_rstd, v_mu) -> torch.Te
                          f"{q.dtype} / {tuple(img.shape)}")
     planes = torch.empty(3, B * Nc, H * 64, device=q.device, dtype=torch.bfloat16)
     _call("mhada_attn_split3_planes", q, q.data_ptr(), img.data_ptr(), fcs.data_ptr(), fcs_mu.data_ptr(),
+          fcs_rstd.data_ptr(), v_mu.data_ptr(), planes.data_ptr(), B, H, Nc, Ns)
+    return planes
+
+
+def _shared_img(what: str, q, img, Ns: int) -> None:
+    H = q.shape[1]
+    ldt = (Ns + 63) // 64 * 64
+    if q.dtype != torch.float32 or img.dtype != torch.bfloat16 or img.shape != (1, H, 576 * ldt) \
+            or not img.is_contiguous():
+        raise ValueError(f"{what}: q must be fp32 and img one style's bf16 [1][{H}][576*{ldt}], got "
+                         f"{q.dtype} / {tuple(img.shape)}")
+
+
+def attn_split3_shared(q, img, Ns: int, fcs, fcs_mu, fcs_rstd, v_mu) -> torch.Tensor:
+    """``mhada_attn_split3_shared``: ``attn_split3`` of B frames against ONE style's plane image
+    [1][H][576 ceil64(Ns)] and v_mu [1][C]; every frame gets ``attn_split3``'s bits."""
+    _need_gpu(q, img, fcs, fcs_mu, fcs_rstd, v_mu)
+    _shared_style("attn_split3_shared", q, fcs, fcs_mu, fcs_rstd, v_mu)
+    _shared_img("attn_split3_shared", q, img, Ns)
+    B, H, Nc, _ = q.shape
+    out = torch.empty(B, Nc, H * 64, device=q.device, dtype=torch.float32)
+    _call("mhada_attn_split3_shared", q, q.data_ptr(), img.data_ptr(), fcs.data_ptr(), fcs_mu.data_ptr(),
+          fcs_rstd.data_ptr(), v_mu.data_ptr(), out.data_ptr(), B, H, Nc, Ns)
+    return out
+
+
+def attn_split3_planes_shared(q, img, Ns: int, fcs, fcs_mu, fcs_rstd, v_mu) -> torch.Tensor:
+    """``mhada_attn_split3_planes_shared``: ``attn_split3_planes`` of B frames against ONE style; planes
+    [3][B * Nc][64 H]."""
+    _need_gpu(q, img, fcs, fcs_mu, fcs_rstd, v_mu)
+    _shared_style("attn_split3_planes_shared", q, fcs, fcs_mu, fcs_rstd, v_mu)
+    _shared_img("attn_split3_planes_shared", q, img, Ns)
+    B, H, Nc, _ = q.shape
+    planes = torch.empty(3, B * Nc, H * 64, device=q.device, dtype=torch.bfloat16)
+    _call("mhada_attn_split3_planes_shared", q, q.data_ptr(), img.data_ptr(), fcs.data_ptr(), fcs_mu.data_ptr(),
           fcs_rstd.data_ptr(), v_mu.data_ptr(), planes.data_ptr(), B, H, Nc, Ns)
     return planes
 

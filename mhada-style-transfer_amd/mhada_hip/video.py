@@ -11,7 +11,8 @@
 * ``VideoStylizer`` — the infer_video.py:58-92 loop: the style is encoded once and, through the
   AdaFormer's per-style cache (engine.style_cache), its K/V projections are reused per frame;
   ``stylize_u8`` returns the cv2-ready u8 frame (mhada_frame_emit, or the decoder's last layer
-  writing it itself: mhada_conv3x3_out3_u8).
+  writing it itself: mhada_conv3x3_out3_u8); ``stylize_clip`` stylises the T frames of a clip in one
+  call, each as if alone, against the one cached style.
 
 The inference forms run the HIP kernels (csrc/warp.hip); the gradient through the warp w.r.t. the
 image (train_video.py temporal losses) runs its HIP adjoint (WarpFn / mhada_warp_bwd).
@@ -137,6 +138,11 @@ def cv2_to_tensor(img, resize: Optional[tuple] = None, device: Optional[torch.de
 STYLIZE_U8_FUSED = False
 
 
+# VideoStylizer.stylize_clip: the most frames one chunk holds when the caller sets no ``max_frames`` (the
+# largest measured, DESIGN.md §3a "Clips")
+CLIP_MAX_FRAMES = 16
+
+
 def tensor_to_cv2(cs: torch.Tensor, bgr: bool = True):
     """The output conversion of infer_video.py:94,110-112 (and exps_video.py / exps_sintel.py), the
     counterpart of cv2_to_tensor: ``cs`` fp32 [3][H][W] or [B][3][H][W] in any range ->
@@ -259,6 +265,101 @@ class VideoStylizer:
         self._host_ev[i].synchronize()
         out = self._host[i].numpy().copy()
         return out[0] if single else out
+
+    def _clip_route(self, frames: torch.Tensor) -> bool:
+        """The one-call clip route covers device modules of the multi-head model at head width 64 with the
+        softmax activation, against a style of batch 1."""
+        ada = self.ada
+        return (frames.is_cuda and hasattr(ada, "adaAttnHead") and self.fs[0].is_cuda and self.fs[0].shape[0] == 1
+                and all(b.head_dim == engine.HEAD_DIM and b.activation_name != "cosine" for b in ada.adaAttnHead))
+
+    @staticmethod
+    def _clip_chunk(T: int, H: int, W: int, device) -> int:
+        """Frames per chunk when the caller sets none: what half of the free device memory holds at about
+        1 KiB per output pixel (the decoder's full-resolution 64-channel maps dominate), at most CLIP_MAX_FRAMES."""
+        free, _ = torch.cuda.mem_get_info(device)
+        free += torch.cuda.memory_reserved(device) - torch.cuda.memory_allocated(device)
+        return max(1, min(T, CLIP_MAX_FRAMES, int(free // 2 // (1024 * H * W))))
+
+    @torch.no_grad()
+    def stylize_clip(self, frames: torch.Tensor, bgr: bool = True, to_host: bool = False, u8: bool = True,
+                     max_frames: Optional[int] = None):
+        """Stylise the T frames of a clip against the one style of ``set_style``, each exactly as if it had
+        been passed alone — NOT ``vit_c(frames)``: the reference ViT attends over the batch axis
+        (vit.py:48,59), so a plain batch of frames mixes them with one another.
+
+        ``frames``: fp32 [T][3][H][W] (0..255, R,G,B planes), or uint8 [T][H][W][3] B,G,R (cv2 frames; rows
+        may be padded), ingested on the device (mhada_frame_ingest).  Returns uint8 [T][H][W][3] in B,G,R
+        (``bgr``) or R,G,B order — ``ops.frame_emit`` of the fp32 result, bit for bit — or with ``u8=False``
+        the clamped fp32 [T][3][H][W]; with ``to_host`` as a numpy array.  ``prev`` / ``cur`` become the
+        last two frames, so ``warping_error`` scores them as after two single calls.
+
+        A chunk of frames is one ``engine.vit_forward(groups=frames)``, the six MHAda blocks against the ONE
+        cached style (the shared-style attention entries: K, V' and the plane image exist once, whatever the
+        number of frames) and the decoder over the chunk.  ``max_frames`` bounds the chunk; None sizes it from
+        the free device memory, at most CLIP_MAX_FRAMES.  A frame's result does not depend on the other
+        frames of the clip, on its place in it, or on the chunking: every chunk runs under
+        ``ops.route_as(T, frames in the chunk)``, so each rule that chooses a kernel form from the rows or the
+        batch of a call chooses what the whole clip of T frames would take.  The forms, and with them the last
+        bits, do depend on T itself (a clip of 3 frames and one of 16 may take different GEMM forms), which is
+        also why the result agrees with ``__call__`` on the frame alone to the forward's parity bound and not
+        bit for bit.
+
+        Measured at 256x512 (DESIGN.md §3a "Clips"): 1.6-1.7x the per-frame loop's frames/s at 2 frames, 3.5x
+        (fp32) and 5.3x (bf16) at 16; one frame per call gains nothing (equal within the per-frame call's own
+        spread), and 1080p frames gain 0-4 % at 2 frames for twice the memory.
+
+        Covered: device modules, the multi-head model at head width 64 with the softmax activation, fp32
+        and bf16, a style of batch 1.  Every other model (the cosine activation, head widths 32 / 128, the
+        single-head width-512 AdaAttnTransformer) and CPU modules evaluate the frames one by one through
+        ``__call__`` / ``stylize_u8``: the same result, only slower."""
+        if self.fs is None:
+            raise RuntimeError("VideoStylizer: call set_style(style_image) first")
+        if not isinstance(frames, torch.Tensor) or frames.dim() != 4:
+            raise ValueError("stylize_clip expects fp32 [T][3][H][W] or uint8 [T][H][W][3] frames, got "
+                             f"{tuple(frames.shape) if isinstance(frames, torch.Tensor) else type(frames).__name__}")
+        if max_frames is not None and max_frames < 1:
+            raise ValueError(f"max_frames must be at least 1, got {max_frames}")
+        if frames.dtype == torch.uint8:
+            if frames.shape[3] != 3:
+                raise ValueError(f"uint8 frames must be [T][H][W][3], got {tuple(frames.shape)}")
+            # CPU: the reference's BGR -> RGB, HWC -> CHW, float (utilities.cv2_to_tensor without resize)
+            frames = ops.frame_ingest(frames, None, bgr=True) if frames.is_cuda else \
+                frames.flip(-1).permute(0, 3, 1, 2).float().contiguous()
+        elif not frames.is_floating_point() or frames.shape[1] != 3:
+            raise ValueError(f"float frames must be [T][3][H][W], got {frames.dtype} {tuple(frames.shape)}")
+        T, _, H, W = frames.shape
+        if T == 0:
+            raise ValueError("stylize_clip needs at least one frame")
+        outs = []
+        if self._clip_route(frames):
+            step = max_frames if max_frames is not None else self._clip_chunk(T, H, W, frames.device)
+            emit = ("bgr" if bgr else "rgb") if (u8 and STYLIZE_U8_FUSED) else None
+            for t0 in range(0, T, step):
+                x = frames[t0:t0 + step]
+                with ops.route_as(T, x.shape[0]):  # the forms of the whole clip, whatever the chunk
+                    fc = engine.vit_forward(self.vit_c, x, groups=x.shape[0])
+                    _, cs = engine.adaformer_forward(self.ada, list(fc), list(self.fs), emit_u8=emit)
+                if u8 and emit is None:
+                    cs = ops.frame_emit(cs, bgr=bgr)
+                outs.append(cs if u8 else cs.clamp(0, 255))
+        else:
+            keep = (self.prev, self.cur)
+            for t in range(T):
+                x = frames[t:t + 1]
+                if not u8:
+                    outs.append(self(x))
+                elif x.is_cuda:
+                    outs.append(self.stylize_u8(x, bgr=bgr))
+                else:
+                    outs.append(torch.from_numpy(tensor_to_cv2(self(x), bgr=bgr)))
+            self.prev, self.cur = keep
+        out = outs[0] if len(outs) == 1 else torch.cat(outs)
+        if T > 1:
+            self.prev, self.cur = out[T - 2:T - 1], out[T - 1:]
+        else:
+            self.prev, self.cur = self.cur, out
+        return out.cpu().numpy() if to_host else out
 
     @torch.no_grad()
     def warping_error(self, flow: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:
