@@ -346,6 +346,26 @@ int mhada_attn_split3_shared(const float* q, const void* img, const float* fcs, 
 int mhada_attn_split3_planes_shared(const float* q, const void* img, const float* fcs, const float* fcs_mu,
                                     const float* fcs_rstd, const float* v_mu, void* planes, int B, int H, int Nc,
                                     int Ns, mhada_stream_t stream);
+/* The shared-style forms of mhada_cosine_attn (head width 64, the linear cosine form) and mhada_attn_hd (head
+ * widths D = 32 | 128, both activations), fp32 and bf16.  Added to ABI 18 WITHOUT a version bump, as the
+ * shared-style entries above: purely additive, found by symbol.
+ * mhada_cosine_attn_shared: mom [H][65][132] (mhada_cosine_moments at B = 1) and v_mu [64H] belong to one style;
+ *   q [B][H][Nc][64], fcs [B][Nc][64H], fcs_mu / fcs_rstd [B][64H] and out [B][Nc][64H] are per frame.  The moments
+ *   depend on the style alone, so a frame costs the style side nothing but reading them.
+ * mhada_attn_hd_shared: kv [H][Ns][2D] and v_mu [D H] belong to one style; q [B][H][Nc][D], fcs [B][Nc][D H],
+ *   fcs_mu / fcs_rstd [B][D H] and out [B][Nc][D H] are per frame.
+ * Each frame's result is bit-identical to the per-batch entry called with the style operands repeated B times
+ * (the same kernel and launch geometry, chosen by the same rules from the same B, Nc and Ns, with a zero batch
+ * stride on the style operands), and the host-side argument checks are the per-batch entries' (null pointers,
+ * non-positive sizes, D outside {32, 128}, alignment).  The fold for mhada_attn_hd_shared is mhada_fold_block_hd
+ * itself, called with the style statistics repeated B times: wq per frame, wkv[0] and v_mu[0] the one style's.
+ * mhada_attn_shared keeps refusing MHADA_ACT_COSINE: the 64-wide cosine route is the linear form. */
+int mhada_cosine_attn_shared(const void* q, const float* mom, const float* fcs, const float* fcs_mu,
+                             const float* fcs_rstd, const float* v_mu, void* out, int dtype, int B, int H,
+                             int Nc, mhada_stream_t stream);
+int mhada_attn_hd_shared(const void* q, const void* kv, const float* fcs, const float* fcs_mu,
+                         const float* fcs_rstd, const float* v_mu, void* out, int dtype, int B, int H,
+                         int D, int Nc, int Ns, int activation, mhada_stream_t stream);
 /* mhada_vit_batch_attn, _split3 and _half2 with the L images taken as `groups` independent calls of
  * L / groups images each, in one launch; bit-identical to the ungrouped entry on each group's slice.
  * Built for L / groups == 1 only (one image per call: the softmax over one key is exactly 1 and the output is

@@ -29,7 +29,8 @@ struct AttnP {
 // The shared-style kernel forms (mhada_attn_shared, mhada_attn_split3_shared, _planes_shared) are this flag
 // in an int template parameter the kernel already has, not a parameter of their own: attn_f32_kernel and
 // attn_bf16_kernel carry it in the activation (ACTF), attn_bf16_fs_kernel in the tile keys (TKF: <8, 384>),
-// attn_bf16_fsq_kernel in the wave count (NWF: <260>, <264>), attn_s3_kernel in the interleave (ILF: 257).  Each
+// attn_bf16_fsq_kernel in the wave count (NWF: <260>, <264>), attn_s3_kernel in the interleave (ILF: 257), and
+// attn_hd_f32_kernel / attn_hd_bf16_kernel (attn_hd.hip, mhada_attn_hd_shared) in the activation.  Each
 // kernel strips it first thing.  A parameter of its own would rename every existing instantiation; this way they
 // keep their mangled names (tools/isa_diff.py pairs kernels by name) and their code.
 constexpr int kAttnShared = 0x100;

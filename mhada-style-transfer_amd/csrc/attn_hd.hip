@@ -14,6 +14,9 @@
 // Block = 4 waves = 128 queries of one (b, h), each wave 32 queries (lane & 31 = query, lane >> 5
 // = h selects the reduction half).  Both dtypes read kv [B][H][Ns][2D] (K | V') directly; there is
 // no transposed image and nothing to cache beside kv.
+// mhada_attn_hd_shared (clips: B frames against ONE style): the same kernels with kAttnShared
+// (attn_common.h) in the ACT parameter, ACTF = ACT | kAttnShared: kv [H][Ns][2D] and v_mu [D H] are
+// read at head hh for every frame b; everything else, the launch geometry included, is unchanged.
 //
 // fp32 (v_mfma_f32_32x32x2_f32, exact fp32): key tiles of TK = 64 (D = 32) / 32 (D = 128) whole kv
 //   rows, register-staged into a double-buffered LDS image sKV[2][TK][2D + 4] (rows padded by 16 B:
@@ -42,7 +45,8 @@ typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 static bool hd_width(int D) { return D == 32 || D == 128; }
 
 // out = sqrt(max(E2 - M^2, 1e-6)) * IN(fcs) + M + v_mu for the wave's 32 queries.
-template <typename T, int D>
+// SHARED (mhada_attn_hd_shared): v_mu is one style's [C] for every frame b, as attn_epilogue's.
+template <typename T, int D, bool SHARED = false>
 MHADA_DEV void epilogue(const AttnP& p, const f32x16 (&O)[D / 16], float l, int b, int hh, int q, int h) {
   constexpr int NB = D / 32;
   const int C = p.H * D;
@@ -52,7 +56,7 @@ MHADA_DEV void epilogue(const AttnP& p, const f32x16 (&O)[D / 16], float l, int 
   const float* fr = p.fcs + ((long long)b * p.Nc + q) * C + hh * D;
   const float* mu = p.fcs_mu + (long long)b * C + hh * D;
   const float* rs = p.fcs_rstd + (long long)b * C + hh * D;
-  const float* vm = p.v_mu + (long long)b * C + hh * D;
+  const float* vm = p.v_mu + (SHARED ? 0LL : (long long)b * C) + hh * D;
   T* orow = reinterpret_cast<T*>(p.out) + ((long long)b * p.Nc + q) * C + hh * D;
 #pragma unroll
   for (int blk = 0; blk < NB; ++blk) {
@@ -83,8 +87,10 @@ MHADA_DEV void epilogue(const AttnP& p, const f32x16 (&O)[D / 16], float l, int 
 // ======================================================================================
 // fp32
 // ======================================================================================
-template <int D, int ACT>
+template <int D, int ACTF>
 __global__ void __launch_bounds__(256, D == 32 ? 2 : 1) attn_hd_f32_kernel(const AttnP p) {
+  constexpr int ACT = ACTF & ~kAttnShared;
+  constexpr bool SHARED = (ACTF & kAttnShared) != 0;
   constexpr int NT = 256, NB = D / 32, TK = D == 32 ? 64 : 32, NKB = TK / 32;
   constexpr int LR = 2 * D + 4;           // padded kv row (floats)
   constexpr int CPR = 2 * D / 4;          // 16-B chunks per kv row
@@ -108,7 +114,8 @@ __global__ void __launch_bounds__(256, D == 32 ? 2 : 1) attn_hd_f32_kernel(const
       for (int e = 0; e < 4; ++e) qreg[4 * i + e] = (q < p.Nc) ? t[e] : 0.f;
     }
   }
-  const float* kvb = reinterpret_cast<const float*>(p.kv) + bh * p.Ns * (2 * D);
+  const long long sbh = SHARED ? hh : bh;  // the style operands' problem index
+  const float* kvb = reinterpret_cast<const float*>(p.kv) + sbh * p.Ns * (2 * D);
 
   f32x4 st[CH];
   auto issue = [&](int key0) {
@@ -190,14 +197,16 @@ __global__ void __launch_bounds__(256, D == 32 ? 2 : 1) attn_hd_f32_kernel(const
     softmax_step<ACT, NKB, 2 * NB>(S, O, m2, l);
     pv(sKV[cb], S);
   }
-  epilogue<float, D>(p, O, l, b, hh, q, h);
+  epilogue<float, D, SHARED>(p, O, l, b, hh, q, h);
 }
 
 // ======================================================================================
 // bf16
 // ======================================================================================
-template <int D, int ACT>
+template <int D, int ACTF>
 __global__ void __launch_bounds__(256, D == 32 ? 2 : 1) attn_hd_bf16_kernel(const AttnP p) {
+  constexpr int ACT = ACTF & ~kAttnShared;
+  constexpr bool SHARED = (ACTF & kAttnShared) != 0;
   constexpr int NT = 256, NB = D / 32, TK = D == 32 ? 128 : 64, NKB = TK / 32, KS = D / 16;
   constexpr int LK = D + 8;    // K rows: D + 8 bf16 (80 / 272 B): conflict-free 16-B row reads
   constexpr int LV = TK + 8;   // V'^T rows: TK keys + 8 (272 / 144 B): conflict-free
@@ -226,7 +235,8 @@ __global__ void __launch_bounds__(256, D == 32 ? 2 : 1) attn_hd_bf16_kernel(cons
       }
     }
   }
-  const bf16* kvb = reinterpret_cast<const bf16*>(p.kv) + bh * p.Ns * (2 * D);
+  const long long sbh = SHARED ? hh : bh;  // the style operands' problem index
+  const bf16* kvb = reinterpret_cast<const bf16*>(p.kv) + sbh * p.Ns * (2 * D);
 
   bf16x8 sk[KCH], sv[VU][2];
   auto load8 = [&](int key, int col) {
@@ -335,13 +345,23 @@ __global__ void __launch_bounds__(256, D == 32 ? 2 : 1) attn_hd_bf16_kernel(cons
     softmax_step<ACT, NKB, 2 * NB>(S, O, m2, l);
     pv(sV[cb], S);
   }
-  epilogue<bf16, D>(p, O, l, b, hh, q, h);
+  epilogue<bf16, D, SHARED>(p, O, l, b, hh, q, h);
 }
 
-template <int D>
+// SHARED: the shared-style forms (mhada_attn_hd_shared), the same kernel and grid with kAttnShared in ACTF.
+template <int D, bool SHARED = false>
 static void launch_attn_hd(const AttnP& p, int dtype, int activation, hipStream_t s) {
   const dim3 grid(p.nblk), blk(256);
-  if (dtype == MHADA_F32) {
+  if constexpr (SHARED) {
+    constexpr int SM = MHADA_ACT_SOFTMAX | kAttnShared, CS = MHADA_ACT_COSINE | kAttnShared;
+    if (dtype == MHADA_F32) {
+      if (activation == MHADA_ACT_SOFTMAX) hipLaunchKernelGGL((attn_hd_f32_kernel<D, SM>), grid, blk, 0, s, p);
+      else hipLaunchKernelGGL((attn_hd_f32_kernel<D, CS>), grid, blk, 0, s, p);
+    } else {
+      if (activation == MHADA_ACT_SOFTMAX) hipLaunchKernelGGL((attn_hd_bf16_kernel<D, SM>), grid, blk, 0, s, p);
+      else hipLaunchKernelGGL((attn_hd_bf16_kernel<D, CS>), grid, blk, 0, s, p);
+    }
+  } else if (dtype == MHADA_F32) {
     if (activation == MHADA_ACT_SOFTMAX) hipLaunchKernelGGL((attn_hd_f32_kernel<D, MHADA_ACT_SOFTMAX>), grid, blk, 0, s, p);
     else hipLaunchKernelGGL((attn_hd_f32_kernel<D, MHADA_ACT_COSINE>), grid, blk, 0, s, p);
   } else {
@@ -489,28 +509,46 @@ int vit_batch_attn_hd(const void* qkv, void* out, int dtype, int L, int ntok, in
 
 using namespace mhada;
 
-extern "C" int mhada_attn_hd(const void* q, const void* kv, const float* fcs, const float* fcs_mu,
-                             const float* fcs_rstd, const float* v_mu, void* out, int dtype, int B, int H, int D,
-                             int Nc, int Ns, int activation, mhada_stream_t s_) {
+// mhada_attn_hd (SHARED = false) and mhada_attn_hd_shared: the same checks, kernel and grid; SHARED reads kv and
+// v_mu of one style for every frame.
+template <bool SHARED>
+static int attn_hd_entry(const char* name_, const void* q, const void* kv, const float* fcs, const float* fcs_mu,
+                         const float* fcs_rstd, const float* v_mu, void* out, int dtype, int B, int H, int D, int Nc,
+                         int Ns, int activation, mhada_stream_t s_) {
+  const std::string name(name_);
   hipStream_t s = (hipStream_t)s_;
   if (!q || !kv || !fcs || !fcs_mu || !fcs_rstd || !v_mu || !out || B <= 0 || H <= 0 || Nc <= 0 || Ns <= 0)
-    return fail("mhada_attn_hd: bad args");
-  if (!hd::hd_width(D)) return fail("mhada_attn_hd: D must be 32 or 128 (64: mhada_attn)");
-  if (dtype != MHADA_F32 && dtype != MHADA_BF16) return fail("mhada_attn_hd: bad dtype");
-  if (activation != MHADA_ACT_SOFTMAX && activation != MHADA_ACT_COSINE) return fail("mhada_attn_hd: bad activation");
+    return fail(name + ": bad args");
+  if (!hd::hd_width(D)) return fail(name + ": D must be 32 or 128 (64: mhada_attn)");
+  if (dtype != MHADA_F32 && dtype != MHADA_BF16) return fail(name + ": bad dtype");
+  if (activation != MHADA_ACT_SOFTMAX && activation != MHADA_ACT_COSINE) return fail(name + ": bad activation");
   if (!aligned16(q) || !aligned16(kv) || !aligned16(fcs) || !aligned16(fcs_mu) ||
       !aligned16(fcs_rstd) || !aligned16(v_mu) || !aligned16(out))
-    return fail("mhada_attn_hd: pointers must be 16-byte aligned");
+    return fail(name + ": pointers must be 16-byte aligned");
   AttnP p = {};
   p.q = q; p.kv = kv; p.fcs = fcs; p.fcs_mu = fcs_mu; p.fcs_rstd = fcs_rstd; p.v_mu = v_mu;
   p.out = out; p.B = B; p.H = H; p.Nc = Nc; p.Ns = Ns;
   p.nqb = (Nc + 127) / 128;
   const long long nblk = (long long)B * H * p.nqb;
-  if (nblk > (1LL << 31) - 1) return fail("mhada_attn_hd: grid too large");
+  if (nblk > (1LL << 31) - 1) return fail(name + ": grid too large");
   p.nblk = (int)nblk;
-  if (D == 32) hd::launch_attn_hd<32>(p, dtype, activation, s);
-  else hd::launch_attn_hd<128>(p, dtype, activation, s);
-  return check_launch("mhada_attn_hd");
+  if (D == 32) hd::launch_attn_hd<32, SHARED>(p, dtype, activation, s);
+  else hd::launch_attn_hd<128, SHARED>(p, dtype, activation, s);
+  return check_launch(name_);
+}
+
+extern "C" int mhada_attn_hd(const void* q, const void* kv, const float* fcs, const float* fcs_mu,
+                             const float* fcs_rstd, const float* v_mu, void* out, int dtype, int B, int H, int D,
+                             int Nc, int Ns, int activation, mhada_stream_t s_) {
+  return attn_hd_entry<false>("mhada_attn_hd", q, kv, fcs, fcs_mu, fcs_rstd, v_mu, out, dtype, B, H, D, Nc, Ns,
+                              activation, s_);
+}
+
+extern "C" int mhada_attn_hd_shared(const void* q, const void* kv, const float* fcs, const float* fcs_mu,
+                                    const float* fcs_rstd, const float* v_mu, void* out, int dtype, int B, int H, int D,
+                                    int Nc, int Ns, int activation, mhada_stream_t s_) {
+  return attn_hd_entry<true>("mhada_attn_hd_shared", q, kv, fcs, fcs_mu, fcs_rstd, v_mu, out, dtype, B, H, D, Nc, Ns,
+                             activation, s_);
 }
 
 extern "C" int mhada_fold_block_hd(const float* wf, const float* wg, const float* wh, const float* bg, const float* bh,

@@ -121,7 +121,11 @@ __global__ void __launch_bounds__(256) cosine_mom_finish_kernel(const float* __r
 // 64 queries of one (b, h) per workgroup; thread (qg, cg) = (t >> 4, t & 15) owns queries
 // 4qg .. 4qg+3 x channels 4cg .. 4cg+3 (M' and E2' of the same channel in the same thread, for the
 // variance).  mhada_attn's epilogue: out = sqrt(max(E2' - M'^2, 1e-6)) * IN(fcs) + (M' + v_mu).
-template <typename T>
+// SHARED (= kAttnShared's role in the attention kernels; mhada_cosine_attn_shared): mom [H][65][132] and v_mu [C]
+// belong to ONE style that every frame b attends to (read at head h); q, fcs, the fcs statistics and out stay per
+// frame.  The kernel had no integer template parameter to carry the flag, so it has this one now: the two existing
+// instantiations are <T, 0> (same code, a new mangled name).
+template <typename T, int SHARED>
 __global__ void __launch_bounds__(256) cosine_attn_kernel(const T* __restrict__ q, const float* __restrict__ mom,
                                                           const float* __restrict__ fcs,
                                                           const float* __restrict__ fcs_mu,
@@ -135,7 +139,7 @@ __global__ void __launch_bounds__(256) cosine_attn_kernel(const T* __restrict__ 
   const long long bh = (long long)b * H + h;
   const int C = 64 * H;
   {
-    const f32x4* src = reinterpret_cast<const f32x4*>(mom + bh * kMomSize);
+    const f32x4* src = reinterpret_cast<const f32x4*>(mom + (SHARED ? (long long)h : bh) * kMomSize);
     for (int i = t; i < kMomSize / 4; i += 256) reinterpret_cast<f32x4*>(ms)[i] = src[i];
   }
   {
@@ -171,7 +175,7 @@ __global__ void __launch_bounds__(256) cosine_attn_kernel(const T* __restrict__ 
   const int col = h * 64 + c0;
   const f32x4 m4 = *reinterpret_cast<const f32x4*>(fcs_mu + (long long)b * C + col);
   const f32x4 r4 = *reinterpret_cast<const f32x4*>(fcs_rstd + (long long)b * C + col);
-  const f32x4 v4 = *reinterpret_cast<const f32x4*>(v_mu + (long long)b * C + col);
+  const f32x4 v4 = *reinterpret_cast<const f32x4*>(v_mu + (SHARED ? 0LL : (long long)b * C) + col);
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const int qq = q0 + 4 * qg + i;
@@ -222,20 +226,36 @@ extern "C" int mhada_cosine_moments(const void* kv, const void* vt, int dtype, i
   return check_launch("mhada_cosine_moments");
 }
 
+// mhada_cosine_attn (SHARED = 0) and mhada_cosine_attn_shared (1): the same checks and grid.
+template <int SHARED>
+static int cosine_attn_entry(const char* name_, const void* q, const float* mom, const float* fcs, const float* fcs_mu,
+                             const float* fcs_rstd, const float* v_mu, void* out, int dtype, int B, int H, int Nc,
+                             mhada_stream_t s_) {
+  const std::string name(name_);
+  const hipStream_t s = (hipStream_t)s_;
+  if (!q || !mom || !fcs || !fcs_mu || !fcs_rstd || !v_mu || !out || B <= 0 || H <= 0 || Nc <= 0)
+    return fail(name + ": bad args");
+  if (dtype != MHADA_F32 && dtype != MHADA_BF16) return fail(name + ": bad dtype");
+  if (B > 65535 || H > 65535) return fail(name + ": B or H > 65535");
+  const dim3 grid((Nc + 63) / 64, H, B);
+  if (dtype == MHADA_F32)
+    hipLaunchKernelGGL((cosine_attn_kernel<float, SHARED>), grid, dim3(256), 0, s, (const float*)q, mom, fcs, fcs_mu,
+                       fcs_rstd, v_mu, (float*)out, H, Nc);
+  else
+    hipLaunchKernelGGL((cosine_attn_kernel<bf16, SHARED>), grid, dim3(256), 0, s, (const bf16*)q, mom, fcs, fcs_mu,
+                       fcs_rstd, v_mu, (bf16*)out, H, Nc);
+  return check_launch(name_);
+}
+
 extern "C" int mhada_cosine_attn(const void* q, const float* mom, const float* fcs, const float* fcs_mu,
                                  const float* fcs_rstd, const float* v_mu, void* out, int dtype, int B, int H, int Nc,
                                  mhada_stream_t s_) {
-  const hipStream_t s = (hipStream_t)s_;
-  if (!q || !mom || !fcs || !fcs_mu || !fcs_rstd || !v_mu || !out || B <= 0 || H <= 0 || Nc <= 0)
-    return fail("mhada_cosine_attn: bad args");
-  if (dtype != MHADA_F32 && dtype != MHADA_BF16) return fail("mhada_cosine_attn: bad dtype");
-  if (B > 65535 || H > 65535) return fail("mhada_cosine_attn: B or H > 65535");
-  const dim3 grid((Nc + 63) / 64, H, B);
-  if (dtype == MHADA_F32)
-    hipLaunchKernelGGL((cosine_attn_kernel<float>), grid, dim3(256), 0, s, (const float*)q, mom, fcs, fcs_mu,
-                       fcs_rstd, v_mu, (float*)out, H, Nc);
-  else
-    hipLaunchKernelGGL((cosine_attn_kernel<bf16>), grid, dim3(256), 0, s, (const bf16*)q, mom, fcs, fcs_mu, fcs_rstd,
-                       v_mu, (bf16*)out, H, Nc);
-  return check_launch("mhada_cosine_attn");
+  return cosine_attn_entry<0>("mhada_cosine_attn", q, mom, fcs, fcs_mu, fcs_rstd, v_mu, out, dtype, B, H, Nc, s_);
+}
+
+extern "C" int mhada_cosine_attn_shared(const void* q, const float* mom, const float* fcs, const float* fcs_mu,
+                                        const float* fcs_rstd, const float* v_mu, void* out, int dtype, int B, int H,
+                                        int Nc, mhada_stream_t s_) {
+  return cosine_attn_entry<1>("mhada_cosine_attn_shared", q, mom, fcs, fcs_mu, fcs_rstd, v_mu, out, dtype, B, H, Nc,
+                              s_);
 }

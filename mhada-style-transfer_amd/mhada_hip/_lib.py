@@ -159,6 +159,8 @@ SIGNATURES = {
     "mhada_attn_shared": (_I, [_vp] * 8 + [_I, _I, _I, _I, _I, _I, _vp]),
     "mhada_attn_split3_shared": (_I, [_vp] * 7 + [_I, _I, _I, _I, _vp]),
     "mhada_attn_split3_planes_shared": (_I, [_vp] * 7 + [_I, _I, _I, _I, _vp]),
+    "mhada_cosine_attn_shared": (_I, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _I, _I, _I, _I, _vp]),
+    "mhada_attn_hd_shared": (_I, [_vp] * 7 + [_I, _I, _I, _I, _I, _I, _I, _vp]),
     "mhada_set_route": (_I, [_I, _I]),
     "mhada_vit_batch_attn_grouped": (_I, [_vp, _vp, _I, _I, _I, _I, _I, _I, _vp]),
     "mhada_vit_batch_attn_split3_grouped": (_I, [_vp, _vp, _c_ll, _I, _I, _I, _I, _I, _vp]),

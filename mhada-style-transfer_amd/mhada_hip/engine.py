@@ -353,8 +353,9 @@ def block_forward(blk, fc: _Feat, fs: Optional[_Feat], fcs: _Feat, dt: torch.dty
     the decoder's first conv (the last block of a bf16 forward).
 
     One style for B > 1 content frames (a style batch of 1, in ``fs`` or in the cache; the clip route of
-    ``VideoStylizer.stylize_clip``): softmax at head width 64 takes the shared-style entries
-    (mhada_attn_shared / attn_split3_shared / attn_split3_planes_shared; the fold is fold_block's), so the
+    ``VideoStylizer.stylize_clip``): the block takes the shared-style entries (softmax at head width 64:
+    mhada_attn_shared / attn_split3_shared / attn_split3_planes_shared; cosine at 64: cosine_attn_shared on the
+    one style's moments; widths 32 / 128: attn_hd_shared; the fold is fold_block's / fold_block_hd's), so the
     style-side tensors exist once; every frame gets the result of its own B = 1 call.  Other
     combinations of unequal batches raise, as before."""
     if blk.head_dim in ops.HD_WIDTHS:
@@ -380,7 +381,7 @@ def block_forward(blk, fc: _Feat, fs: Optional[_Feat], fcs: _Feat, dt: torch.dty
             raise ValueError(f"channel mismatch: block expects {C}")
         mu_s, rstd_s = fs.stats()
         Bs = fs.t.shape[0]
-    shared = Bs == 1 and B > 1 and act == ACT_SOFTMAX  # one style, B frames
+    shared = Bs == 1 and B > 1  # one style, B frames
     if Bs != B and not shared:
         raise ValueError(f"cached style batch {Bs} != content batch {B}" if cached else
                          f"style batch {Bs} != content batch {B}")
@@ -423,7 +424,8 @@ def block_forward(blk, fc: _Feat, fs: Optional[_Feat], fcs: _Feat, dt: torch.dty
     if act == ACT_COSINE:
         ops.cosine_prep(q, None)
         with _timed("mhada_attn"):
-            att = ops.cosine_attn(q, mom, fcs.t, mu_o, rstd_o, v_mu)  # [B][Nc][C] dt
+            att = (ops.cosine_attn_shared if shared else ops.cosine_attn)(
+                q, mom, fcs.t, mu_o, rstd_o, v_mu)  # [B][Nc][C] dt
     elif split_attn and ops.F32_SPLIT_OUTPROJ and _split3_fills(B * Nc, C, dev):
         # the attention writes its output as bf16 planes and out_conv runs as a SPLIT3 GEMM (no fp32 att)
         with _timed("mhada_attn"):
@@ -456,7 +458,8 @@ def _block_forward_hd(blk, fc: _Feat, fs: Optional[_Feat], fcs: _Feat, dt: torch
     """block_forward at head_dim 32 | 128 (csrc/attn_hd.hip): fold_block_hd, the Q and K|V' projections on
     mhada_gemm (N = K = D and N = 2D, K = D; no vt image: the attention reads kv), cosine_prep_hd for the
     cosine activation (the flash loop, not the 64-wide linear form), attn_hd, the out_conv GEMM.  ``side``
-    caches the style-side tensors (mu_s, rstd_s, kv) exactly as on the 64 path."""
+    caches the style-side tensors (mu_s, rstd_s, kv) exactly as on the 64 path.  One style for B > 1 frames
+    (style batch 1): fold_block_hd_shared, K|V' and its cosine_prep_hd at the style's batch, attn_hd_shared."""
     prep = block_prep(blk, dt)
     H, D = blk.num_heads, blk.head_dim
     C = H * D
@@ -466,36 +469,41 @@ def _block_forward_hd(blk, fc: _Feat, fs: Optional[_Feat], fcs: _Feat, dt: torch
     act = ACT_COSINE if blk.activation_name == "cosine" else ACT_SOFTMAX
     if cached:
         mu_s, rstd_s, kv, Ns = side["mu_s"], side["rstd_s"], side["kv"], side["Ns"]
-        if side["B"] != B:
-            raise ValueError(f"cached style batch {side['B']} != content batch {B}")
+        Bs = side["B"]
     else:
         if fs.t.shape[2] != C:
             raise ValueError(f"channel mismatch: block expects {C}")
         mu_s, rstd_s = fs.stats()
+        Bs = fs.t.shape[0]
+    shared = Bs == 1 and B > 1  # one style, B frames
+    if Bs != B and not shared:
+        raise ValueError(f"cached style batch {Bs} != content batch {B}" if cached else
+                         f"style batch {Bs} != content batch {B}")
     if Cc != C or fcs.t.shape[2] != C:
         raise ValueError(f"channel mismatch: block expects {C}")
     mu_c, rstd_c = fc.stats()
     mu_o, rstd_o = fcs.stats()
-    wq, wkv, bkv, v_mu = ops.fold_block_hd(prep["wf"], prep["wg"], prep["wh"], prep["bg"], prep["bh"],
-                                           rstd_c, mu_s, rstd_s, dt, ops.LOG2E if act == ACT_SOFTMAX else 1.0)
+    fold = ops.fold_block_hd_shared if shared else ops.fold_block_hd
+    wq, wkv, bkv, v_mu = fold(prep["wf"], prep["wg"], prep["wh"], prep["bg"], prep["bh"],
+                              rstd_c, mu_s, rstd_s, dt, ops.LOG2E if act == ACT_SOFTMAX else 1.0)
     dev = fc.t.device
     q = torch.empty(B, H, Nc, D, device=dev, dtype=dt)
     ops.gemm(a=fc.t, w=wq, c=q, M=Nc, N=D, K=D, compute=dt, lda=C, sa=(Nc * C, D), nb=(B, H), a_mu=mu_c,
              smu=(C, D), ldw=D, sw=(H * D * D, D * D), bias=prep["bf"], sb=(0, D), ldc=D, sc=(H * Nc * D, Nc * D))
     if not cached:
         Ns = fs.t.shape[1]
-        kv = torch.empty(B, H, Ns, 2 * D, device=dev, dtype=dt)
-        ops.gemm(a=fs.t, w=wkv, c=kv, M=Ns, N=2 * D, K=D, compute=dt, lda=C, sa=(Ns * C, D), nb=(B, H), a_mu=mu_s,
+        kv = torch.empty(Bs, H, Ns, 2 * D, device=dev, dtype=dt)
+        ops.gemm(a=fs.t, w=wkv, c=kv, M=Ns, N=2 * D, K=D, compute=dt, lda=C, sa=(Ns * C, D), nb=(Bs, H), a_mu=mu_s,
                  smu=(C, D), ldw=D, sw=(H * 2 * D * D, 2 * D * D), bias=bkv, sb=(0, 2 * D), ldc=2 * D,
                  sc=(H * Ns * 2 * D, Ns * 2 * D))
         if act == ACT_COSINE:
             ops.cosine_prep_hd(None, kv)
         if side is not None:
-            side.update(mu_s=mu_s, rstd_s=rstd_s, kv=kv, Ns=Ns, B=B)
+            side.update(mu_s=mu_s, rstd_s=rstd_s, kv=kv, Ns=Ns, B=Bs)
     if act == ACT_COSINE:
         ops.cosine_prep_hd(q, None)
     with _timed("mhada_attn"):
-        att = ops.attn_hd(q, kv, fcs.t, mu_o, rstd_o, v_mu, act)  # [B][Nc][C] dt
+        att = (ops.attn_hd_shared if shared else ops.attn_hd)(q, kv, fcs.t, mu_o, rstd_o, v_mu, act)  # [B][Nc][C] dt
     out = torch.empty(B * Nc, C, device=dev, dtype=torch.float32)
     t16 = torch.empty(B * Nc, C, device=dev, dtype=torch.bfloat16) if want_bf16 else None
     ops.gemm(a=att.view(B * Nc, C), w=prep["w_out"], c=out, M=B * Nc, N=C, K=C, compute=dt, lda=C, ldw=C,

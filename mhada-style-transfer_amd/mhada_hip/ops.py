@@ -977,6 +977,9 @@ def cosine_prep(q: Optional[torch.Tensor], kv: Optional[torch.Tensor]) -> None:
     """L2-normalise Q rows and/or the K half of KV rows in place (either may be None)."""
     _need_gpu(q, kv)
     ref = q if q is not None else kv
+    if q is not None and kv is not None and q.shape[:2] != kv.shape[:2]:
+        raise ValueError(f"cosine_prep: q {tuple(q.shape)} and kv {tuple(kv.shape)} differ in batch or heads; "
+                         "normalise them in two calls")
     B, H = ref.shape[0], ref.shape[1]
     Nc = q.shape[2] if q is not None else 0
     Ns = kv.shape[2] if kv is not None else 0
@@ -1055,6 +1058,22 @@ def mhada_attn_shared(q, kv, vt, fcs, fcs_mu, fcs_rstd, v_mu) -> torch.Tensor:
     return out
 
 
+def cosine_attn_shared(q, mom, fcs, fcs_mu, fcs_rstd, v_mu) -> torch.Tensor:
+    """``mhada_cosine_attn_shared``: ``cosine_attn`` of B frames (normalised q [B][H][Nc][64], fcs and statistics
+    per frame) against ONE style (mom [1][H][65][132] of cosine_moments, v_mu [1][C]); every frame gets the bits
+    of ``cosine_attn`` with mom and v_mu repeated B times.  fp32 or bf16."""
+    _need_gpu(q, mom, fcs, fcs_mu, fcs_rstd, v_mu)
+    _shared_style("cosine_attn_shared", q, fcs, fcs_mu, fcs_rstd, v_mu)
+    B, H, Nc, _ = q.shape
+    if mom.shape != (1, H, 65, 132) or mom.dtype != torch.float32 or not mom.is_contiguous():
+        raise ValueError(f"cosine_attn_shared: mom must be one style's contiguous fp32 [1][{H}][65][132], got "
+                         f"{tuple(mom.shape)} {mom.dtype}")
+    out = torch.empty(B, Nc, H * 64, device=q.device, dtype=q.dtype)
+    _call("mhada_cosine_attn_shared", q, q.data_ptr(), mom.data_ptr(), fcs.data_ptr(), fcs_mu.data_ptr(),
+          fcs_rstd.data_ptr(), v_mu.data_ptr(), out.data_ptr(), dt_code(q.dtype), B, H, Nc)
+    return out
+
+
 HD_WIDTHS = (32, 128)  # head widths of the *_hd entry points (csrc/attn_hd.hip); 64 has its own kernels
 
 
@@ -1129,6 +1148,45 @@ def attn_hd(q, kv, fcs, fcs_mu, fcs_rstd, v_mu, activation: int) -> torch.Tensor
     out = torch.empty(B, Nc, C, device=q.device, dtype=q.dtype)
     _call("mhada_attn_hd", q, q.data_ptr(), kv.data_ptr(), fcs.data_ptr(), fcs_mu.data_ptr(), fcs_rstd.data_ptr(),
           v_mu.data_ptr(), out.data_ptr(), dt_code(q.dtype), B, H, D, Nc, Ns, activation)
+    return out
+
+
+def fold_block_hd_shared(wf, wg, wh, bg, bh, rstd_c, mu_s, rstd_s, dtype: torch.dtype, kscale: float = LOG2E):
+    """``fold_block_hd`` for B content frames (rstd_c [B][C]) against ONE style (mu_s, rstd_s [1][C]): wq
+    [B][H][D][D] per frame; wkv [1][H][2D][D], bkv and v_mu [1][C] of the style.  The existing entry with the
+    style statistics repeated, as ``fold_block_shared``: no kernel of its own, so the bits are fold_block_hd's."""
+    B, C = rstd_c.shape
+    if mu_s.shape != (1, C) or rstd_s.shape != (1, C):
+        raise ValueError(f"fold_block_hd_shared: the style statistics must be [1][{C}], got {tuple(mu_s.shape)} / "
+                         f"{tuple(rstd_s.shape)}")
+    wq, wkv, bkv, v_mu = fold_block_hd(wf, wg, wh, bg, bh, rstd_c, mu_s.expand(B, C).contiguous(),
+                                       rstd_s.expand(B, C).contiguous(), dtype, kscale)
+    return wq, wkv[:1], bkv, v_mu[:1]
+
+
+def attn_hd_shared(q, kv, fcs, fcs_mu, fcs_rstd, v_mu, activation: int) -> torch.Tensor:
+    """``mhada_attn_hd_shared``: ``attn_hd`` of B frames (q [B][H][Nc][D], fcs and statistics per frame) against
+    ONE style (kv [1][H][Ns][2D], v_mu [1][C]); every frame gets the bits of ``attn_hd`` with kv and v_mu repeated
+    B times.  D = 32 | 128, both activations, fp32 or bf16."""
+    _need_gpu(q, kv, fcs, fcs_mu, fcs_rstd, v_mu)
+    if q.dim() != 4 or kv.dim() != 4:
+        raise ValueError(f"attn_hd_shared: needs q [B][H][Nc][D] and kv [1][H][Ns][2D], got {tuple(q.shape)} / "
+                         f"{tuple(kv.shape)}")
+    B, H, Nc, D = q.shape
+    Ns = kv.shape[2]
+    _hd_width("attn_hd_shared", D)
+    C = H * D
+    if kv.shape != (1, H, Ns, 2 * D) or kv.dtype != q.dtype or not q.is_contiguous() or not kv.is_contiguous():
+        raise ValueError(f"attn_hd_shared: needs contiguous q [B][H][Nc][{D}] and one style's kv [1][H][Ns][{2 * D}] of "
+                         f"one dtype, got {tuple(q.shape)} {q.dtype} / {tuple(kv.shape)} {kv.dtype}")
+    if Nc <= 0 or Ns <= 0:
+        raise ValueError(f"attn_hd_shared: needs Nc > 0 and Ns > 0, got {Nc} / {Ns}")
+    for t, shape in ((fcs, (B, Nc, C)), (fcs_mu, (B, C)), (fcs_rstd, (B, C)), (v_mu, (1, C))):
+        if tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError(f"attn_hd_shared: needs contiguous fp32 {shape}, got {tuple(t.shape)} {t.dtype}")
+    out = torch.empty(B, Nc, C, device=q.device, dtype=q.dtype)
+    _call("mhada_attn_hd_shared", q, q.data_ptr(), kv.data_ptr(), fcs.data_ptr(), fcs_mu.data_ptr(),
+          fcs_rstd.data_ptr(), v_mu.data_ptr(), out.data_ptr(), dt_code(q.dtype), B, H, D, Nc, Ns, activation)
     return out
 
 

@@ -267,11 +267,12 @@ class VideoStylizer:
         return out[0] if single else out
 
     def _clip_route(self, frames: torch.Tensor) -> bool:
-        """The one-call clip route covers device modules of the multi-head model at head width 64 with the
-        softmax activation, against a style of batch 1."""
+        """The one-call clip route covers device modules of the multi-head model at head widths 32, 64 and 128
+        (16, 8 and 4 heads) with either activation, against a style of batch 1."""
         ada = self.ada
+        widths = (engine.HEAD_DIM,) + tuple(ops.HD_WIDTHS)
         return (frames.is_cuda and hasattr(ada, "adaAttnHead") and self.fs[0].is_cuda and self.fs[0].shape[0] == 1
-                and all(b.head_dim == engine.HEAD_DIM and b.activation_name != "cosine" for b in ada.adaAttnHead))
+                and all(b.head_dim in widths for b in ada.adaAttnHead))
 
     @staticmethod
     def _clip_chunk(T: int, H: int, W: int, device) -> int:
@@ -295,8 +296,8 @@ class VideoStylizer:
         last two frames, so ``warping_error`` scores them as after two single calls.
 
         A chunk of frames is one ``engine.vit_forward(groups=frames)``, the six MHAda blocks against the ONE
-        cached style (the shared-style attention entries: K, V' and the plane image exist once, whatever the
-        number of frames) and the decoder over the chunk.  ``max_frames`` bounds the chunk; None sizes it from
+        cached style (the shared-style attention entries: K, V', the plane image and the cosine activation's
+        moments exist once, whatever the number of frames) and the decoder over the chunk.  ``max_frames`` bounds the chunk; None sizes it from
         the free device memory, at most CLIP_MAX_FRAMES.  A frame's result does not depend on the other
         frames of the clip, on its place in it, or on the chunking: every chunk runs under
         ``ops.route_as(T, frames in the chunk)``, so each rule that chooses a kernel form from the rows or the
@@ -309,10 +310,10 @@ class VideoStylizer:
         (fp32) and 5.3x (bf16) at 16; one frame per call gains nothing (equal within the per-frame call's own
         spread), and 1080p frames gain 0-4 % at 2 frames for twice the memory.
 
-        Covered: device modules, the multi-head model at head width 64 with the softmax activation, fp32
-        and bf16, a style of batch 1.  Every other model (the cosine activation, head widths 32 / 128, the
-        single-head width-512 AdaAttnTransformer) and CPU modules evaluate the frames one by one through
-        ``__call__`` / ``stylize_u8``: the same result, only slower."""
+        Covered: device modules, the multi-head model at head widths 32, 64 and 128 (16, 8 and 4 heads) with
+        the softmax or the cosine activation, fp32 and bf16, a style of batch 1.  The single-head width-512
+        AdaAttnTransformer, any other head width, a style of another batch and CPU modules evaluate the frames
+        one by one through ``__call__`` / ``stylize_u8``: the same result, only slower."""
         if self.fs is None:
             raise RuntimeError("VideoStylizer: call set_style(style_image) first")
         if not isinstance(frames, torch.Tensor) or frames.dim() != 4:

@@ -1,13 +1,15 @@
 """Frames/s of VideoStylizer.stylize_clip against the per-frame loop over stylize_u8, in one process.
 
     python tools/clip_throughput.py [--hw 256x512] [--style 256] [--T 1,2,4,8,16] [--rounds 7] [--dtypes fp32,bf16]
+                                    [--heads 8] [--activation softmax]
 
 Per dtype and T: `rounds` alternating rounds of (per-frame loop over T frames, the same loop again, one
 stylize_clip(max_frames=T)), each timed with device events after one untimed warm-up round; prints the medians
 with the min-max spread, the loop's A-against-A spread (its two timings in the same round), the ratio of the
 medians, and the peak device memory of each route (above what is held before the call).  Frames are uint8
 B,G,R [T][H][W][3]; the style is 256^2.  Seeded weights (mhada_hip.recipe), so the numbers are reproducible
-without a checkpoint.
+without a checkpoint.  --heads 4 | 8 | 16 (head widths 128 / 64 / 32, the ViTs built with the same head count)
+and --activation softmax | cosine choose the model family; the defaults are the 8-head softmax model.
 """
 import argparse
 import os
@@ -50,21 +52,30 @@ def main():
     ap.add_argument("--T", default="1,2,4,8,16")
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--dtypes", default="fp32,bf16")
+    ap.add_argument("--heads", type=int, default=8, choices=(4, 8, 16))
+    ap.add_argument("--activation", default="softmax", choices=("softmax", "cosine"))
     ap.add_argument("--no-clip", action="store_true", help="the per-frame loop alone (a tree without stylize_clip)")
     ap.add_argument("--clip-only", action="store_true", help="the clip call alone, untimed rounds (under a kernel trace)")
     a = ap.parse_args()
     H, W = map(int, a.hw.split("x"))
     dev = torch.device("cuda:0")
     print(f"# {torch.cuda.get_device_name(0)}; frames {H}x{W} u8, style {a.style}^2, {a.rounds} rounds; ms per call")
+    default = a.heads == 8 and a.activation == "softmax"
+    if not default:
+        print(f"# model: {a.heads} heads (head width {512 // a.heads}), {a.activation}")
+    kw = {} if default else dict(num_heads=a.heads)
+    akw = {} if default else dict(num_heads=a.heads, activation=a.activation)
     for dn in a.dtypes.split(","):
         dt = dict(fp32=torch.float32, bf16=torch.bfloat16)[dn]
-        vc = load_recipe(network.VisionTransformer(pos_embedding=True), "vit_c").to(dev).eval()
-        vs = load_recipe(network.VisionTransformer(pos_embedding=False), "vit_s").to(dev).eval()
-        ada = load_recipe(network.AdaAttnTransformerMultiHead(), "ada").to(dev).eval()
+        vc = load_recipe(network.VisionTransformer(pos_embedding=True, **kw), "vit_c").to(dev).eval()
+        vs = load_recipe(network.VisionTransformer(pos_embedding=False, **kw), "vit_s").to(dev).eval()
+        ada = load_recipe(network.AdaAttnTransformerMultiHead(**akw), "ada").to(dev).eval()
         for m in (vc, vs, ada):
             m.compute_dtype = dt
         st = VideoStylizer(vc, vs, ada)
         st.set_style(seeded_image(1, a.style, a.style, 2).to(dev))
+        if not default:
+            print(f"# {dn}: clip route {'on' if st._clip_route(torch.empty(0, device=dev)) else 'off (per-frame loop)'}")
         for T in map(int, a.T.split(",")):
             g = torch.Generator().manual_seed(T)
             u8 = torch.randint(0, 256, (T, H, W, 3), generator=g, dtype=torch.uint8).to(dev)
