@@ -776,7 +776,39 @@ int mhada_rows_normalize(const float* x, const float* mu, const float* rs, float
  * out: [B][3][Ho][Wo] fp32. */
 int mhada_frame_ingest(const void* frames, int B, int H, int W, long long row_bytes, int bgr, float* out,
                        int Ho, int Wo, mhada_stream_t stream);
-/* Frame emit, the inverse (infer_video.py:94,110-112: cs.clamp(0,255) -> permute(1,2,0) -> numpy
+/* Image ingest (infer_image.py:69,76 and every other image entry point:
+ * Image.open(p).convert("RGB").resize((Wo, Ho), Image.BILINEAR) then toTensor255), csrc/image_ingest.hip.
+ * Added to ABI 18 WITHOUT a version bump (purely additive, found by symbol; see the _hd entries).
+ * PIL's 8-bit BILINEAR resample, bit for bit: per axis a triangle filter widened by the scale factor
+ * when shrinking, 22-bit fixed-point coefficients, per channel
+ *   out = clamp((2^21 + sum_t in[xmin + t] * k[t]) >> 22, 0, 255)  in 32-bit integers;
+ * the horizontal pass first (only if Wo != W) ROUNDED TO u8, then the vertical pass (only if Ho != H) on
+ * that u8 image; the same size on both axes is a copy.  No floating point before the final toTensor255
+ * (utilities.py:11-16: /255 then *255 in fp32).
+ * frames: [B][H][W][3] u8, rows of row_bytes >= 3W, images H * row_bytes apart (as mhada_frame_ingest);
+ * bgr != 0 swaps channels 0 and 2 on the way in (PIL images are R,G,B: 0).
+ * Tables, DEVICE memory, built by the caller in float64 exactly as Resample.c's precompute_coeffs /
+ * normalize_coeffs_8bpc do (ops.pil_bilinear_tables; never recomputed here, where an FMA contraction
+ * would change a coefficient): per axis coef int32 [n_out][ksize] and bounds int32 [n_out][2] =
+ * (xmin, count), count <= ksize, xmin + count <= n_in; the x pair for W -> Wo, the y pair for H -> Ho.
+ * A pair is read only when its axis changes size (else it may be null).  Entries outside those ranges
+ * are clipped to them (wrong pixels, never an out-of-bounds read).
+ * Outputs, either may be null, not both: out_u8 [B][Ho][Wo][3] R,G,B, rows of out_row_bytes >= 3Wo,
+ * images Ho * out_row_bytes apart, bytes 3Wo..out_row_bytes-1 of a row never written; out_f32
+ * [B][3][Ho][Wo] fp32, the model input.
+ * Two launches when both axes change: horizontal into `work` (u8 [B][H][Wo][3], at least
+ * mhada_image_resize_work(B, H, W, Ho, Wo) bytes, 0 when one axis or none changes and work may be
+ * null), then vertical; the source is read once.  One launch otherwise.
+ * A null frames pointer, both outputs null, a size <= 0, row_bytes < 3W, out_row_bytes < 3Wo, out_f32 or
+ * a table not 4-byte aligned, a needed table null or ksize <= 0, W or Wo above (2^31 - 1) / 3, B > 65535,
+ * H > 16 * 65535 when Wo != W, Ho > 4 * 65535, or a needed workspace null or short return MHADA_ERR_ARG
+ * before any launch. */
+long long mhada_image_resize_work(int B, int H, int W, int Ho, int Wo);
+int mhada_image_resize(const void* frames, int B, int H, int W, long long row_bytes, int bgr, const int* coef_x,
+                       const int* bounds_x, int ksize_x, const int* coef_y, const int* bounds_y, int ksize_y,
+                       void* out_u8, long long out_row_bytes, float* out_f32, int Ho, int Wo, void* work,
+                       long long work_bytes, mhada_stream_t stream);
+/* Frame emit, the inverse of mhada_frame_ingest (infer_video.py:94,110-112: cs.clamp(0,255) -> permute(1,2,0) -> numpy
  * astype(uint8) -> cv2.cvtColor(RGB2BGR)).  x: fp32 [B][3][H][W] contiguous, any range, R,G,B planes.
  * frames: u8 [B][H][row_bytes], pixel (y, x) at bytes 3x..3x+2 of its row, B,G,R when bgr != 0 and
  * R,G,B otherwise; row_bytes >= 3W, images H * row_bytes apart; bytes 3W..row_bytes-1 of a row are

@@ -114,6 +114,9 @@ SIGNATURES = {
     "mhada_temporal_loss_bwd": (_I, [_vp] * 14 + [_I, _I, _I, _I, _vp]),
     "mhada_flow_mask_resize": (_I, [_vp, _vp, _vp, _vp, _I, _I, _I, _I, _I, _vp]),
     "mhada_frame_ingest": (_I, [_vp, _I, _I, _I, _c_ll, _I, _vp, _I, _I, _vp]),
+    "mhada_image_resize_work": (_c_ll, [_I, _I, _I, _I, _I]),
+    "mhada_image_resize": (_I, [_vp, _I, _I, _I, _c_ll, _I, _vp, _vp, _I, _vp, _vp, _I, _vp, _c_ll, _vp, _I, _I, _vp,
+                                _c_ll, _vp]),
     "mhada_frame_emit": (_I, [_vp, _I, _I, _I, _vp, _c_ll, _I, _vp]),
     "mhada_conv3x3_out3_u8": (_I, [_vp, _I, _vp, _vp, _vp, _c_ll, _I, _I, _I, _I, _I, _vp]),
     "mhada_gemm_tn_splits": (_I, [_I, _I, _I]),

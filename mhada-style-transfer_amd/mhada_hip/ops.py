@@ -10,9 +10,11 @@ from __future__ import annotations
 
 import contextlib
 import ctypes
+import functools
 import math
 from typing import Optional
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -1885,6 +1887,84 @@ def _u8_input(frames: torch.Tensor, what: str) -> torch.Tensor:
     if B > 1 and frames.stride(0) != H * frames.stride(1):
         frames = frames.contiguous()
     return frames
+
+
+# ---- image ingest: PIL's BILINEAR resize (csrc/image_ingest.hip) --------------------------
+@functools.lru_cache(maxsize=None)
+def pil_bilinear_tables(n_in: int, n_out: int):
+    """The coefficient tables of PIL's 8-bit BILINEAR resample of one axis, ``n_in -> n_out`` (Resample.c:
+    precompute_coeffs then normalize_coeffs_8bpc), built in IEEE double with every operation in PIL's order:
+    ``(coef, bounds)``, read-only CPU int32 arrays [n_out][ksize] and [n_out][2] = (xmin, count).  Row ``i`` of
+    ``coef`` holds ``int(0.5 + w * 2^22)`` of the normalised triangle weights of output index ``i`` (zeros past
+    ``count``).  Cached per size pair; needs no GPU."""
+    n_in, n_out = int(n_in), int(n_out)
+    if n_in <= 0 or n_out <= 0:
+        raise ValueError(f"pil_bilinear_tables: sizes must be positive, got {n_in} -> {n_out}")
+    scale = n_in / n_out
+    fs = max(scale, 1.0)
+    support = 1.0 * fs
+    ksize = int(math.ceil(support)) * 2 + 1
+    inv = 1.0 / fs
+    coef = np.zeros((n_out, ksize), dtype=np.int32)
+    bounds = np.zeros((n_out, 2), dtype=np.int32)
+    for xx in range(n_out):
+        center = (xx + 0.5) * scale
+        xmin = max(int(center - support + 0.5), 0)
+        xmax = min(int(center + support + 0.5), n_in) - xmin
+        w = [max(0.0, 1.0 - abs((x + xmin - center + 0.5) * inv)) for x in range(xmax)]
+        ww = 0.0
+        for v in w:  # a running sum in index order, as the C loop adds (not numpy's pairwise sum)
+            ww += v
+        if ww != 0.0:
+            w = [v / ww for v in w]
+        coef[xx, :xmax] = [int(0.5 + v * 4194304.0) for v in w]
+        bounds[xx] = (xmin, xmax)
+    coef.setflags(write=False)
+    bounds.setflags(write=False)
+    return coef, bounds
+
+
+_RESIZE_TABLES = {}
+
+
+def _resize_tables(n_in: int, n_out: int, device):
+    """pil_bilinear_tables(n_in, n_out) as device tensors, uploaded once per (n_in, n_out, device)."""
+    key = (int(n_in), int(n_out), torch.device(device))
+    t = _RESIZE_TABLES.get(key)
+    if t is None:
+        coef, bounds = pil_bilinear_tables(key[0], key[1])
+        t = _RESIZE_TABLES[key] = (torch.from_numpy(coef.copy()).to(device), torch.from_numpy(bounds.copy()).to(device))
+    return t
+
+
+def image_resize(frames: torch.Tensor, out_hw, bgr: bool = False, want_u8: bool = True, want_f32: bool = True,
+                 out_u8: Optional[torch.Tensor] = None):
+    """``mhada_image_resize``: u8 images [B][H][W][3] (or one [H][W][3]; rows may be padded) resized to
+    ``out_hw`` = (Ho, Wo) bit for bit as ``PIL.Image.resize(..., Image.BILINEAR)`` does -> ``(u8, f32)``: the
+    resized u8 R,G,B images [B][Ho][Wo][3] (``want_u8``; what metrics.score consumes) and the fp32
+    [B][3][Ho][Wo] model input toTensor255 makes of them (``want_f32``); an output not wanted is None.
+    ``bgr`` swaps channels 0 and 2 on the way in (PIL images are R,G,B).  ``out_u8``: a u8 [B][Ho][Wo][3]
+    tensor to write in place; its rows may be padded (a view of a wider buffer), the padding bytes are not
+    touched."""
+    frames = _u8_input(frames, "image_resize")
+    _need_gpu(frames, out_u8)
+    B, H, W, _ = frames.shape
+    Ho, Wo = int(out_hw[0]), int(out_hw[1])
+    if Ho <= 0 or Wo <= 0:
+        raise ValueError(f"image_resize: out_hw must be positive, got {(Ho, Wo)}")
+    if not (want_u8 or want_f32 or out_u8 is not None):
+        raise ValueError("image_resize: want_u8 or want_f32 (or both)")
+    dev = frames.device
+    u8 = _u8_frames(out_u8, B, Ho, Wo, dev) if (want_u8 or out_u8 is not None) else None
+    f32 = torch.empty(B, 3, Ho, Wo, device=dev, dtype=torch.float32) if want_f32 else None
+    cx, bx = _resize_tables(W, Wo, dev) if Wo != W else (None, None)
+    cy, by = _resize_tables(H, Ho, dev) if Ho != H else (None, None)
+    nwork = int(_lib.load().mhada_image_resize_work(B, H, W, Ho, Wo))
+    work = torch.empty(nwork, device=dev, dtype=torch.uint8) if nwork else None
+    _call("mhada_image_resize", frames, frames.data_ptr(), B, H, W, frames.stride(1), int(bgr),
+          _ptr(cx), _ptr(bx), 0 if cx is None else cx.shape[1], _ptr(cy), _ptr(by), 0 if cy is None else cy.shape[1],
+          _ptr(u8), 0 if u8 is None else u8.stride(1), _ptr(f32), Ho, Wo, _ptr(work), nwork)
+    return u8, f32
 
 
 _SSIM_WINDOW = None
