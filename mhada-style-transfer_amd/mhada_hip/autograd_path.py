@@ -173,6 +173,11 @@ def _softmax_or_cosine(q, k, activation: str):
     return s / s.sum(dim=-1, keepdim=True)  # adaDecoder.py:24-34
 
 
+def _train_op(name: str, q: torch.Tensor):
+    """ops.<name> at head width 64, ops.<name>_hd at 32 | 128 (looked up per call: tests patch them by name)."""
+    return getattr(ops, name if q.shape[-1] == 64 else name + "_hd")
+
+
 class MHAdaAttnFn(torch.autograd.Function):
     """The attention core of adaDecoder.py:186-198 on the HIP training kernels
     (csrc/attn_train.hip, one kernel family for the head widths 32, 64 and 128):
@@ -185,8 +190,7 @@ class MHAdaAttnFn(torch.autograd.Function):
     @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
     def forward(ctx, q, k, v, x):
         q, k, v, x = (t.contiguous() for t in (q, k, v, x))
-        fwd = ops.attn_train_fwd if q.shape[-1] == 64 else ops.attn_train_fwd_hd
-        out, mo, lse = fwd(q, k, v, x)
+        out, mo, lse = _train_op("attn_train_fwd", q)(q, k, v, x)
         ctx.save_for_backward(q, k, v, x, mo, lse)
         return out
 
@@ -200,18 +204,11 @@ class MHAdaAttnFn(torch.autograd.Function):
         # the dQ kernel alone
         dq_only = ATTN_DQ_ONLY and not ctx.needs_input_grad[1] and not ctx.needs_input_grad[2]
         dk = dv = None
-        if q.shape[-1] == 64:
-            dx, dmo, dd = ops.attn_train_bwd_prep(dout.contiguous(), x, mo)
-            if dq_only:
-                dq = ops.attn_train_dq(q, k, v, lse, dmo, dd)
-            else:
-                dq, dk, dv = ops.attn_train_bwd(q, k, v, lse, dmo, dd)
+        dx, dmo, dd = _train_op("attn_train_bwd_prep", q)(dout.contiguous(), x, mo)
+        if dq_only:
+            dq = _train_op("attn_train_dq", q)(q, k, v, lse, dmo, dd)
         else:
-            dx, dmo, dd = ops.attn_train_bwd_prep_hd(dout.contiguous(), x, mo)
-            if dq_only:
-                dq = ops.attn_train_dq_hd(q, k, v, lse, dmo, dd)
-            else:
-                dq, dk, dv = ops.attn_train_bwd_hd(q, k, v, lse, dmo, dd)
+            dq, dk, dv = _train_op("attn_train_bwd", q)(q, k, v, lse, dmo, dd)
         return dq, dk, dv, dx
 
 

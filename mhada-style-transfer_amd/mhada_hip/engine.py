@@ -344,137 +344,52 @@ class _Feat:
 
 def block_forward(blk, fc: _Feat, fs: Optional[_Feat], fcs: _Feat, dt: torch.dtype,
                   side: Optional[dict] = None, want_bf16: bool = False) -> _Feat:
-    """AdaAttnMultiHead.forward (adaDecoder.py:162-206).
+    """AdaAttnMultiHead.forward (adaDecoder.py:162-206) at head width D = 64 (its own kernels) or 32 | 128
+    (ops.HD_WIDTHS, csrc/attn_hd.hip): the weight fold, the Q and K|V' projections on mhada_gemm (N = K = D
+    and N = 2D, K = D), the attention, the out_conv GEMM.
 
-    ``side`` carries the block's style-only tensors (IN statistics of fs, the K|V' projection and
-    its V'^T image): when it is filled they are reused (fs may then be None), when it is an empty
-    dict they are computed and stored into it (the per-style cache of adaformer_forward).
+    ``side`` carries the block's style-only tensors (IN statistics of fs and the style side of the attention,
+    below): when it is filled they are reused (fs may then be None), when it is an empty dict they are
+    computed and stored into it (the per-style cache of adaformer_forward).
     ``want_bf16``: the out_conv GEMM also writes a bf16 copy of the block output (``.t16``) for
     the decoder's first conv (the last block of a bf16 forward).
 
+    The style side and the attention, per width and activation (``side`` keys in brackets):
+      * 64, fp32 softmax with ops.F32_SPLIT_ATTN: kv_proj_split3 writes the bf16 plane image [img];
+        attn_split3, or attn_split3_planes + a SPLIT3 out_conv (linear_split3) where its tiles fill the chip.
+      * 64, other softmax: the K|V' GEMM with the vt epilogue (K rows into kv, V' into the transposed
+        V'^T | V'^2^T image) [kv, vt]; mhada_attn.
+      * 64, cosine: on top of that cosine_prep and cosine_moments, the linear form's style moments [mom];
+        cosine_prep of q, cosine_attn.
+      * 32 / 128: fold_block_hd, the K|V' GEMM without vt (the attention reads kv) [kv], cosine_prep_hd of kv
+        and of q for cosine (the flash loop, not the linear form); attn_hd.
+
     One style for B > 1 content frames (a style batch of 1, in ``fs`` or in the cache; the clip route of
-    ``VideoStylizer.stylize_clip``): the block takes the shared-style entries (softmax at head width 64:
-    mhada_attn_shared / attn_split3_shared / attn_split3_planes_shared; cosine at 64: cosine_attn_shared on the
-    one style's moments; widths 32 / 128: attn_hd_shared; the fold is fold_block's / fold_block_hd's), so the
-    style-side tensors exist once; every frame gets the result of its own B = 1 call.  Other
-    combinations of unequal batches raise, as before."""
-    if blk.head_dim in ops.HD_WIDTHS:
-        return _block_forward_hd(blk, fc, fs, fcs, dt, side, want_bf16)
-    if blk.head_dim != HEAD_DIM:
-        raise ValueError("the HIP MHAda kernels implement head_dim (qkv_dim/num_heads) in {32, 64, 128}, "
-                         f"got {blk.head_dim}")
-    prep = block_prep(blk, dt)
-    H = blk.num_heads
-    C = H * HEAD_DIM
-    B, Nc, Cc = fc.t.shape
-    cached = bool(side)
-    mom = img = kv = vt = None
-    act = ACT_COSINE if blk.activation_name == "cosine" else ACT_SOFTMAX
-    # fp32 softmax: the SPLIT3 attention on bf16 planes of K and V'^T | V'^2^T (csrc/attn_split3.hip)
-    split_attn = act == ACT_SOFTMAX and dt == torch.float32 and ops.F32_SPLIT_ATTN
-    if cached:
-        mu_s, rstd_s, mom, Ns = side["mu_s"], side["rstd_s"], side.get("mom"), side["Ns"]
-        kv, vt, img = side.get("kv"), side.get("vt"), side.get("img")
-        Bs = side["B"]
-    else:
-        if fs.t.shape[2] != C:
-            raise ValueError(f"channel mismatch: block expects {C}")
-        mu_s, rstd_s = fs.stats()
-        Bs = fs.t.shape[0]
-    shared = Bs == 1 and B > 1  # one style, B frames
-    if Bs != B and not shared:
-        raise ValueError(f"cached style batch {Bs} != content batch {B}" if cached else
-                         f"style batch {Bs} != content batch {B}")
-    if Cc != C or fcs.t.shape[2] != C:
-        raise ValueError(f"channel mismatch: block expects {C}")
-    mu_c, rstd_c = fc.stats()
-    mu_o, rstd_o = fcs.stats()
-    fold = ops.fold_block_shared if shared else ops.fold_block
-    wq, wkv, bkv, v_mu = fold(prep["wf"], prep["wg"], prep["wh"], prep["bg"], prep["bh"],
-                              rstd_c, mu_s, rstd_s, dt, ops.LOG2E if act == ACT_SOFTMAX else 1.0)
-    dev = fc.t.device
-    q = torch.empty(B, H, Nc, HEAD_DIM, device=dev, dtype=dt)
-    ops.gemm(a=fc.t, w=wq, c=q, M=Nc, N=HEAD_DIM, K=HEAD_DIM, compute=dt, lda=C, sa=(Nc * C, HEAD_DIM),
-             nb=(B, H), a_mu=mu_c, smu=(C, HEAD_DIM), ldw=HEAD_DIM, sw=(H * HEAD_DIM * HEAD_DIM, HEAD_DIM * HEAD_DIM),
-             bias=prep["bf"], sb=(0, HEAD_DIM), ldc=HEAD_DIM, sc=(H * Nc * HEAD_DIM, Nc * HEAD_DIM))
-    if not cached and split_attn:
-        Ns = fs.t.shape[1]
-        # K|V' projection written straight as the SPLIT3 attention's bf16 plane image (no fp32 kv / vt)
-        img = ops.kv_proj_split3(fs.t, mu_s, wkv, bkv)
-        if side is not None:
-            side.update(mu_s=mu_s, rstd_s=rstd_s, img=img, Ns=Ns, B=Bs)
-    elif not cached:
-        Ns = fs.t.shape[1]
-        # K|V' projection: K rows into kv[..., :64] (the attention's K operand), V' straight into
-        # the transposed V'^T | V'^2^T image vt (the GEMM's vt epilogue; kv[..., 64:] unused)
-        kv = torch.empty(Bs, H, Ns, 2 * HEAD_DIM, device=dev, dtype=dt)
-        ldt = (Ns + 63) // 64 * 64
-        vt = torch.empty(Bs, H, 2 * HEAD_DIM, ldt, device=dev, dtype=dt)
-        ops.gemm(a=fs.t, w=wkv, c=kv, M=Ns, N=2 * HEAD_DIM, K=HEAD_DIM, compute=dt, lda=C, sa=(Ns * C, HEAD_DIM),
-                 nb=(Bs, H), a_mu=mu_s, smu=(C, HEAD_DIM), ldw=HEAD_DIM,
-                 sw=(H * 2 * HEAD_DIM * HEAD_DIM, 2 * HEAD_DIM * HEAD_DIM), bias=bkv, sb=(0, 2 * HEAD_DIM),
-                 ldc=2 * HEAD_DIM, sc=(H * Ns * 2 * HEAD_DIM, Ns * 2 * HEAD_DIM),
-                 vt=vt, ldt=ldt, svt=(H * 2 * HEAD_DIM * ldt, 2 * HEAD_DIM * ldt))
-        if act == ACT_COSINE:
-            # the cosine activation's linear form: the style-side moments replace the Nc x Ns loop
-            ops.cosine_prep(None, kv)
-            mom = ops.cosine_moments(kv, vt)
-        if side is not None:
-            side.update(mu_s=mu_s, rstd_s=rstd_s, kv=kv, vt=vt, mom=mom, Ns=Ns, B=Bs)
-    if act == ACT_COSINE:
-        ops.cosine_prep(q, None)
-        with _timed("mhada_attn"):
-            att = (ops.cosine_attn_shared if shared else ops.cosine_attn)(
-                q, mom, fcs.t, mu_o, rstd_o, v_mu)  # [B][Nc][C] dt
-    elif split_attn and ops.F32_SPLIT_OUTPROJ and _split3_fills(B * Nc, C, dev):
-        # the attention writes its output as bf16 planes and out_conv runs as a SPLIT3 GEMM (no fp32 att)
-        with _timed("mhada_attn"):
-            att3 = (ops.attn_split3_planes_shared if shared else ops.attn_split3_planes)(
-                q, img, Ns, fcs.t, mu_o, rstd_o, v_mu)  # [3][B Nc][C] bf16
-        if "w_out_split3" not in prep:
-            with torch.no_grad():
-                prep["w_out_split3"] = ops.split3_weight(prep["w_out"])
-        out = ops.linear_split3(att3, prep["w_out_split3"], prep["b_out"], torch.float32)
-        return _Feat(out.view(B, Nc, C), fc.h, fc.w)
-    elif split_attn:
-        with _timed("mhada_attn"):
-            att = (ops.attn_split3_shared if shared else ops.attn_split3)(
-                q, img, Ns, fcs.t, mu_o, rstd_o, v_mu)  # [B][Nc][C] fp32
-    else:
-        with _timed("mhada_attn"):
-            att = ops.mhada_attn_shared(q, kv, vt, fcs.t, mu_o, rstd_o, v_mu) if shared else \
-                ops.mhada_attn(q, kv, vt, fcs.t, mu_o, rstd_o, v_mu, act)  # [B][Nc][C] dt
-    out = torch.empty(B * Nc, C, device=dev, dtype=torch.float32)
-    t16 = torch.empty(B * Nc, C, device=dev, dtype=torch.bfloat16) if want_bf16 else None
-    ops.gemm(a=att.view(B * Nc, C), w=prep["w_out"], c=out, M=B * Nc, N=C, K=C, compute=dt, lda=C, ldw=C,
-             bias=prep["b_out"], ldc=C, c2=t16, ldc2=C)
-    f = _Feat(out.view(B, Nc, C), fc.h, fc.w)
-    f.t16 = None if t16 is None else t16.view(B, Nc, C)
-    return f
-
-
-def _block_forward_hd(blk, fc: _Feat, fs: Optional[_Feat], fcs: _Feat, dt: torch.dtype,
-                      side: Optional[dict], want_bf16: bool) -> _Feat:
-    """block_forward at head_dim 32 | 128 (csrc/attn_hd.hip): fold_block_hd, the Q and K|V' projections on
-    mhada_gemm (N = K = D and N = 2D, K = D; no vt image: the attention reads kv), cosine_prep_hd for the
-    cosine activation (the flash loop, not the 64-wide linear form), attn_hd, the out_conv GEMM.  ``side``
-    caches the style-side tensors (mu_s, rstd_s, kv) exactly as on the 64 path.  One style for B > 1 frames
-    (style batch 1): fold_block_hd_shared, K|V' and its cosine_prep_hd at the style's batch, attn_hd_shared."""
-    prep = block_prep(blk, dt)
+    ``VideoStylizer.stylize_clip``): the block takes the shared-style entries (fold_block_shared /
+    fold_block_hd_shared, the style side at the style's batch, mhada_attn_shared / attn_split3_shared /
+    attn_split3_planes_shared / cosine_attn_shared / attn_hd_shared), so the style-side tensors exist once;
+    every frame gets the result of its own B = 1 call.  Other combinations of unequal batches raise."""
     H, D = blk.num_heads, blk.head_dim
+    hd = D in ops.HD_WIDTHS
+    if not hd and D != HEAD_DIM:
+        raise ValueError("the HIP MHAda kernels implement head_dim (qkv_dim/num_heads) in {32, 64, 128}, "
+                         f"got {D}")
+    prep = block_prep(blk, dt)
     C = H * D
     B, Nc, Cc = fc.t.shape
     cached = bool(side)
-    kv = None
     act = ACT_COSINE if blk.activation_name == "cosine" else ACT_SOFTMAX
+    # fp32 softmax at 64: the SPLIT3 attention on bf16 planes of K and V'^T | V'^2^T (csrc/attn_split3.hip)
+    split_attn = not hd and act == ACT_SOFTMAX and dt == torch.float32 and ops.F32_SPLIT_ATTN
+    kv = vt = mom = img = None
     if cached:
-        mu_s, rstd_s, kv, Ns = side["mu_s"], side["rstd_s"], side["kv"], side["Ns"]
-        Bs = side["B"]
+        mu_s, rstd_s, Ns, Bs = side["mu_s"], side["rstd_s"], side["Ns"], side["B"]
+        kv, vt, mom, img = side.get("kv"), side.get("vt"), side.get("mom"), side.get("img")
     else:
         if fs.t.shape[2] != C:
             raise ValueError(f"channel mismatch: block expects {C}")
         mu_s, rstd_s = fs.stats()
-        Bs = fs.t.shape[0]
+        Ns, Bs = fs.t.shape[1], fs.t.shape[0]
     shared = Bs == 1 and B > 1  # one style, B frames
     if Bs != B and not shared:
         raise ValueError(f"cached style batch {Bs} != content batch {B}" if cached else
@@ -483,27 +398,67 @@ def _block_forward_hd(blk, fc: _Feat, fs: Optional[_Feat], fcs: _Feat, dt: torch
         raise ValueError(f"channel mismatch: block expects {C}")
     mu_c, rstd_c = fc.stats()
     mu_o, rstd_o = fcs.stats()
-    fold = ops.fold_block_hd_shared if shared else ops.fold_block_hd
+    if hd:
+        fold = ops.fold_block_hd_shared if shared else ops.fold_block_hd
+    else:
+        fold = ops.fold_block_shared if shared else ops.fold_block
     wq, wkv, bkv, v_mu = fold(prep["wf"], prep["wg"], prep["wh"], prep["bg"], prep["bh"],
                               rstd_c, mu_s, rstd_s, dt, ops.LOG2E if act == ACT_SOFTMAX else 1.0)
     dev = fc.t.device
     q = torch.empty(B, H, Nc, D, device=dev, dtype=dt)
     ops.gemm(a=fc.t, w=wq, c=q, M=Nc, N=D, K=D, compute=dt, lda=C, sa=(Nc * C, D), nb=(B, H), a_mu=mu_c,
              smu=(C, D), ldw=D, sw=(H * D * D, D * D), bias=prep["bf"], sb=(0, D), ldc=D, sc=(H * Nc * D, Nc * D))
-    if not cached:
-        Ns = fs.t.shape[1]
+    if not cached and split_attn:
+        # K|V' projection written straight as the SPLIT3 attention's bf16 plane image (no fp32 kv / vt)
+        img = ops.kv_proj_split3(fs.t, mu_s, wkv, bkv)
+        built = dict(img=img)
+    elif not cached:
         kv = torch.empty(Bs, H, Ns, 2 * D, device=dev, dtype=dt)
-        ops.gemm(a=fs.t, w=wkv, c=kv, M=Ns, N=2 * D, K=D, compute=dt, lda=C, sa=(Ns * C, D), nb=(Bs, H), a_mu=mu_s,
-                 smu=(C, D), ldw=D, sw=(H * 2 * D * D, 2 * D * D), bias=bkv, sb=(0, 2 * D), ldc=2 * D,
-                 sc=(H * Ns * 2 * D, Ns * 2 * D))
-        if act == ACT_COSINE:
+        vt_args = {}
+        if not hd:
+            # K rows into kv[..., :64] (the attention's K operand), V' straight into the transposed
+            # V'^T | V'^2^T image vt (the GEMM's vt epilogue; kv[..., 64:] unused)
+            ldt = (Ns + 63) // 64 * 64
+            vt = torch.empty(Bs, H, 2 * D, ldt, device=dev, dtype=dt)
+            vt_args = dict(vt=vt, ldt=ldt, svt=(H * 2 * D * ldt, 2 * D * ldt))
+        ops.gemm(a=fs.t, w=wkv, c=kv, M=Ns, N=2 * D, K=D, compute=dt, lda=C, sa=(Ns * C, D), nb=(Bs, H),
+                 a_mu=mu_s, smu=(C, D), ldw=D, sw=(H * 2 * D * D, 2 * D * D), bias=bkv, sb=(0, 2 * D),
+                 ldc=2 * D, sc=(H * Ns * 2 * D, Ns * 2 * D), **vt_args)
+        if act == ACT_COSINE and hd:
             ops.cosine_prep_hd(None, kv)
-        if side is not None:
-            side.update(mu_s=mu_s, rstd_s=rstd_s, kv=kv, Ns=Ns, B=Bs)
+        elif act == ACT_COSINE:
+            # the cosine activation's linear form: the style-side moments replace the Nc x Ns loop
+            ops.cosine_prep(None, kv)
+            mom = ops.cosine_moments(kv, vt)
+        built = dict(kv=kv) if hd else dict(kv=kv, vt=vt, mom=mom)
+    if not cached and side is not None:
+        side.update(mu_s=mu_s, rstd_s=rstd_s, Ns=Ns, B=Bs, **built)
     if act == ACT_COSINE:
-        ops.cosine_prep_hd(q, None)
+        (ops.cosine_prep_hd if hd else ops.cosine_prep)(q, None)
+    # fp32 softmax where the tiles fill the chip: the attention writes its output as bf16 planes and out_conv
+    # runs as a SPLIT3 GEMM (no fp32 att)
+    planes = split_attn and ops.F32_SPLIT_OUTPROJ and _split3_fills(B * Nc, C, dev)
     with _timed("mhada_attn"):
-        att = (ops.attn_hd_shared if shared else ops.attn_hd)(q, kv, fcs.t, mu_o, rstd_o, v_mu, act)  # [B][Nc][C] dt
+        if hd:
+            att = (ops.attn_hd_shared if shared else ops.attn_hd)(q, kv, fcs.t, mu_o, rstd_o, v_mu, act)
+        elif act == ACT_COSINE:
+            att = (ops.cosine_attn_shared if shared else ops.cosine_attn)(q, mom, fcs.t, mu_o, rstd_o, v_mu)
+        elif planes:
+            att = (ops.attn_split3_planes_shared if shared else ops.attn_split3_planes)(
+                q, img, Ns, fcs.t, mu_o, rstd_o, v_mu)  # [3][B Nc][C] bf16
+        elif split_attn:
+            att = (ops.attn_split3_shared if shared else ops.attn_split3)(
+                q, img, Ns, fcs.t, mu_o, rstd_o, v_mu)  # [B][Nc][C] fp32
+        elif shared:
+            att = ops.mhada_attn_shared(q, kv, vt, fcs.t, mu_o, rstd_o, v_mu)
+        else:
+            att = ops.mhada_attn(q, kv, vt, fcs.t, mu_o, rstd_o, v_mu, act)  # [B][Nc][C] dt
+    if planes:
+        if "w_out_split3" not in prep:
+            with torch.no_grad():
+                prep["w_out_split3"] = ops.split3_weight(prep["w_out"])
+        out = ops.linear_split3(att, prep["w_out_split3"], prep["b_out"], torch.float32)
+        return _Feat(out.view(B, Nc, C), fc.h, fc.w)
     out = torch.empty(B * Nc, C, device=dev, dtype=torch.float32)
     t16 = torch.empty(B * Nc, C, device=dev, dtype=torch.bfloat16) if want_bf16 else None
     ops.gemm(a=att.view(B * Nc, C), w=prep["w_out"], c=out, M=B * Nc, N=C, K=C, compute=dt, lda=C, ldw=C,

@@ -706,36 +706,6 @@ def vit_batch_attn(qkv: torch.Tensor, L: int, ntok: int, heads: int, groups: int
 VIT_ATTN_SPLIT3_MAX_L = 8  # mhada_vit_batch_attn_split3 refuses longer batch axes (and head widths != 64)
 
 
-def vit_batch_attn_split3(qkv: torch.Tensor, L: int, ntok: int, heads: int) -> torch.Tensor:
-    """``mhada_vit_batch_attn_split3``: ``vit_batch_attn`` of fp32 qkv [L][ntok][3C] with the result as its three
-    bf16 planes [3][L * ntok][C] (bit-identical to ``split3_rows`` of the fp32 output), the A operand of
-    ``linear_split3``.  head_dim 64 and L <= 8; other shapes raise."""
-    _need_gpu(qkv)
-    if qkv.dtype != torch.float32 or not qkv.is_contiguous():
-        raise ValueError("vit_batch_attn_split3 needs contiguous float32 qkv")
-    C = qkv.shape[-1] // 3
-    planes = torch.empty(3, L * ntok, C, device=qkv.device, dtype=torch.bfloat16)
-    _call("mhada_vit_batch_attn_split3", qkv, qkv.data_ptr(), planes.data_ptr(), L * ntok * C, L, ntok, heads,
-          C // heads)
-    return planes
-
-
-def vit_batch_attn_half2(qkv: torch.Tensor, L: int, ntok: int, heads: int, out_scale: torch.Tensor) -> torch.Tensor:
-    """``mhada_vit_batch_attn_half2``: ``vit_batch_attn`` of fp32 qkv [L][ntok][3C] with out_scale[c] times the
-    result as two fp16 planes [2][L * ntok][C] (bit-identical to ``_half2_planes`` of that product), the A
-    operand of ``linear_half2_planes``.  head_dim 64 and L <= 8; other shapes raise."""
-    _need_gpu(qkv, out_scale)
-    C = qkv.shape[-1] // 3
-    if qkv.dtype != torch.float32 or not qkv.is_contiguous():
-        raise ValueError("vit_batch_attn_half2 needs contiguous float32 qkv")
-    if out_scale.dtype != torch.float32 or out_scale.numel() != C or not out_scale.is_contiguous():
-        raise ValueError("vit_batch_attn_half2: out_scale must be contiguous float32 [C]")
-    planes = torch.empty(2, L * ntok, C, device=qkv.device, dtype=torch.float16)
-    _call("mhada_vit_batch_attn_half2", qkv, qkv.data_ptr(), planes.data_ptr(), L * ntok * C, out_scale.data_ptr(),
-          L, ntok, heads, C // heads)
-    return planes
-
-
 def _one_per_group(what: str, L: int, groups: int) -> None:
     if groups < 1 or L % groups:
         raise ValueError(f"{what}: L must be a positive multiple of groups")
@@ -744,50 +714,63 @@ def _one_per_group(what: str, L: int, groups: int) -> None:
                          "vit_batch_attn(groups=) loops over any grouping")
 
 
+def _vit_batch_attn(what: str, planes: int, qkv, L: int, ntok: int, heads: int, out_scale=None, groups=None):
+    """The one-launch forms of ``vit_batch_attn`` (entry point "mhada_" + what) on qkv [L][ntok][3C].  ``planes``
+    0: the output [L][ntok][C] in qkv's dtype; 3: fp32 qkv, the output as its three bf16 planes
+    [3][L * ntok][C]; 2: fp32 qkv, out_scale[c] times the output as two fp16 planes [2][L * ntok][C].
+    ``groups``: the grouped entries (the L images as that many independent calls; one image per group)."""
+    _need_gpu(qkv, out_scale)
+    if groups is not None:
+        _one_per_group(what, L, groups)
+    C = qkv.shape[-1] // 3
+    if (planes and qkv.dtype != torch.float32) or not qkv.is_contiguous():
+        raise ValueError(f"{what} needs contiguous {'float32 ' if planes else ''}qkv")
+    if planes == 2 and (out_scale.dtype != torch.float32 or out_scale.numel() != C or not out_scale.is_contiguous()):
+        raise ValueError(f"{what}: out_scale must be contiguous float32 [C]")
+    if planes:
+        out = torch.empty(planes, L * ntok, C, device=qkv.device,
+                          dtype=torch.bfloat16 if planes == 3 else torch.float16)
+        form = (L * ntok * C,) + ((out_scale.data_ptr(),) if planes == 2 else ())
+    else:
+        out = torch.empty(L, ntok, C, device=qkv.device, dtype=qkv.dtype)
+        form = (dt_code(qkv.dtype),)
+    _call("mhada_" + what, qkv, qkv.data_ptr(), out.data_ptr(), *form, L, ntok, heads, C // heads,
+          *(() if groups is None else (groups,)))
+    return out
+
+
+def vit_batch_attn_split3(qkv: torch.Tensor, L: int, ntok: int, heads: int) -> torch.Tensor:
+    """``mhada_vit_batch_attn_split3``: ``vit_batch_attn`` of fp32 qkv [L][ntok][3C] with the result as its three
+    bf16 planes [3][L * ntok][C] (bit-identical to ``split3_rows`` of the fp32 output), the A operand of
+    ``linear_split3``.  head_dim 64 and L <= 8; other shapes raise."""
+    return _vit_batch_attn("vit_batch_attn_split3", 3, qkv, L, ntok, heads)
+
+
+def vit_batch_attn_half2(qkv: torch.Tensor, L: int, ntok: int, heads: int, out_scale: torch.Tensor) -> torch.Tensor:
+    """``mhada_vit_batch_attn_half2``: ``vit_batch_attn`` of fp32 qkv [L][ntok][3C] with out_scale[c] times the
+    result as two fp16 planes [2][L * ntok][C] (bit-identical to ``_half2_planes`` of that product), the A
+    operand of ``linear_half2_planes``.  head_dim 64 and L <= 8; other shapes raise."""
+    return _vit_batch_attn("vit_batch_attn_half2", 2, qkv, L, ntok, heads, out_scale)
+
+
 def vit_batch_attn_grouped(qkv: torch.Tensor, L: int, ntok: int, heads: int, groups: int) -> torch.Tensor:
     """``mhada_vit_batch_attn_grouped``: ``vit_batch_attn`` with the L images of qkv [L][ntok][3C] taken as
     ``groups`` independent calls, in ONE launch (the group comes from the grid); bit-identical to
     ``vit_batch_attn`` on each group's slice.  Built for L / groups == 1 (the clip route): the output is V."""
-    _need_gpu(qkv)
-    _one_per_group("vit_batch_attn_grouped", L, groups)
-    if not qkv.is_contiguous():
-        raise ValueError("vit_batch_attn_grouped needs contiguous qkv")
-    C = qkv.shape[-1] // 3
-    out = torch.empty(L, ntok, C, device=qkv.device, dtype=qkv.dtype)
-    _call("mhada_vit_batch_attn_grouped", qkv, qkv.data_ptr(), out.data_ptr(), dt_code(qkv.dtype), L, ntok, heads,
-          C // heads, groups)
-    return out
+    return _vit_batch_attn("vit_batch_attn_grouped", 0, qkv, L, ntok, heads, groups=groups)
 
 
 def vit_batch_attn_split3_grouped(qkv: torch.Tensor, L: int, ntok: int, heads: int, groups: int) -> torch.Tensor:
     """``mhada_vit_batch_attn_split3_grouped``: the grouped form of ``vit_batch_attn_split3`` (planes
     [3][L * ntok][C]); L / groups == 1, head_dim 64."""
-    _need_gpu(qkv)
-    _one_per_group("vit_batch_attn_split3_grouped", L, groups)
-    if qkv.dtype != torch.float32 or not qkv.is_contiguous():
-        raise ValueError("vit_batch_attn_split3_grouped needs contiguous float32 qkv")
-    C = qkv.shape[-1] // 3
-    planes = torch.empty(3, L * ntok, C, device=qkv.device, dtype=torch.bfloat16)
-    _call("mhada_vit_batch_attn_split3_grouped", qkv, qkv.data_ptr(), planes.data_ptr(), L * ntok * C, L, ntok,
-          heads, C // heads, groups)
-    return planes
+    return _vit_batch_attn("vit_batch_attn_split3_grouped", 3, qkv, L, ntok, heads, groups=groups)
 
 
 def vit_batch_attn_half2_grouped(qkv: torch.Tensor, L: int, ntok: int, heads: int, out_scale: torch.Tensor,
                                  groups: int) -> torch.Tensor:
     """``mhada_vit_batch_attn_half2_grouped``: the grouped form of ``vit_batch_attn_half2`` (fp16 planes
     [2][L * ntok][C]); L / groups == 1, head_dim 64."""
-    _need_gpu(qkv, out_scale)
-    _one_per_group("vit_batch_attn_half2_grouped", L, groups)
-    C = qkv.shape[-1] // 3
-    if qkv.dtype != torch.float32 or not qkv.is_contiguous():
-        raise ValueError("vit_batch_attn_half2_grouped needs contiguous float32 qkv")
-    if out_scale.dtype != torch.float32 or out_scale.numel() != C or not out_scale.is_contiguous():
-        raise ValueError("vit_batch_attn_half2_grouped: out_scale must be contiguous float32 [C]")
-    planes = torch.empty(2, L * ntok, C, device=qkv.device, dtype=torch.float16)
-    _call("mhada_vit_batch_attn_half2_grouped", qkv, qkv.data_ptr(), planes.data_ptr(), L * ntok * C,
-          out_scale.data_ptr(), L, ntok, heads, C // heads, groups)
-    return planes
+    return _vit_batch_attn("vit_batch_attn_half2_grouped", 2, qkv, L, ntok, heads, out_scale, groups)
 
 
 def pos_embed(pos: torch.Tensor, oh: int, ow: int) -> torch.Tensor:
@@ -937,33 +920,76 @@ def instnorm_stats(x: torch.Tensor, eps: float = 1e-5):
 LOG2E = 1.4426950408889634
 
 
+HD_WIDTHS = (32, 128)  # head widths of the *_hd entry points (csrc/attn_hd.hip); 64 has its own kernels
+
+
+def _hd_width(what: str, D: int) -> None:
+    if D not in HD_WIDTHS:
+        raise ValueError(f"{what}: head width must be 32 or 128 (64 has its own entry point), got {D}")
+
+
+def _fold_block(what: str, hd: bool, wf, wg, wh, bg, bh, rstd_c, mu_s, rstd_s, dtype, kscale):
+    """fold_block (``hd`` False: W* [H][64][64], no checks of its own) and fold_block_hd (W* [H][D][D], D = 32 |
+    128, every operand checked); entry point "mhada_" + what, which at ``hd`` also takes D."""
+    ts = (wf, wg, wh, bg, bh, rstd_c, mu_s, rstd_s)
+    if hd:
+        _need_gpu(*ts)
+    B, C = rstd_c.shape
+    H, D = wf.shape[0], wf.shape[1] if hd else 64
+    if hd:
+        _hd_width(what, D)
+        for t, shape in ((wf, (H, D, D)), (wg, (H, D, D)), (wh, (H, D, D)), (bg, (H, D)), (bh, (H, D)),
+                         (rstd_c, (B, H * D)), (mu_s, (B, H * D)), (rstd_s, (B, H * D))):
+            if tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous():
+                raise ValueError(f"{what}: needs contiguous fp32 {shape}, got {tuple(t.shape)} {t.dtype}")
+        dt_code(dtype)
+    dev = wf.device
+    wq = torch.empty(B, H, D, D, device=dev, dtype=dtype)
+    wkv = torch.empty(B, H, 2 * D, D, device=dev, dtype=dtype)
+    bkv = torch.empty(H, 2 * D, device=dev, dtype=torch.float32)
+    v_mu = torch.empty(B, C, device=dev, dtype=torch.float32)
+    if not hd:  # fold_block has always checked the device after allocating
+        _need_gpu(*ts)
+    _call("mhada_" + what, wf, *(t.data_ptr() for t in ts), wq.data_ptr(), wkv.data_ptr(), bkv.data_ptr(),
+          v_mu.data_ptr(), kscale, dt_code(dtype), B, H, *((D,) if hd else ()))
+    return wq, wkv, bkv, v_mu
+
+
+def _fold_block_shared(what: str, fold, wf, wg, wh, bg, bh, rstd_c, mu_s, rstd_s, dtype, kscale):
+    """``fold`` (fold_block | fold_block_hd) with one style's statistics [1][C] repeated for the B frames."""
+    B, C = rstd_c.shape
+    if mu_s.shape != (1, C) or rstd_s.shape != (1, C):
+        raise ValueError(f"{what}: the style statistics must be [1][{C}], got {tuple(mu_s.shape)} / "
+                         f"{tuple(rstd_s.shape)}")
+    wq, wkv, bkv, v_mu = fold(wf, wg, wh, bg, bh, rstd_c, mu_s.expand(B, C).contiguous(),
+                              rstd_s.expand(B, C).contiguous(), dtype, kscale)
+    return wq, wkv[:1], bkv, v_mu[:1]
+
+
 def fold_block(wf, wg, wh, bg, bh, rstd_c, mu_s, rstd_s, dtype: torch.dtype, kscale: float = LOG2E):
     """Per-call weight fold of one MHAda block (include/mhada_hip.h).  kscale = log2(e) puts K
     in the softmax attention's log2 units (mhada_attn's K contract); 1.0 for cosine."""
-    B, C = rstd_c.shape
-    H = wf.shape[0]
-    dev = wf.device
-    wq = torch.empty(B, H, 64, 64, device=dev, dtype=dtype)
-    wkv = torch.empty(B, H, 128, 64, device=dev, dtype=dtype)
-    bkv = torch.empty(H, 128, device=dev, dtype=torch.float32)
-    v_mu = torch.empty(B, C, device=dev, dtype=torch.float32)
-    _need_gpu(wf, wg, wh, bg, bh, rstd_c, mu_s, rstd_s)
-    _call("mhada_fold_block", wf, wf.data_ptr(), wg.data_ptr(), wh.data_ptr(), bg.data_ptr(), bh.data_ptr(),
-          rstd_c.data_ptr(), mu_s.data_ptr(), rstd_s.data_ptr(), wq.data_ptr(), wkv.data_ptr(), bkv.data_ptr(),
-          v_mu.data_ptr(), kscale, dt_code(dtype), B, H)
-    return wq, wkv, bkv, v_mu
+    return _fold_block("fold_block", False, wf, wg, wh, bg, bh, rstd_c, mu_s, rstd_s, dtype, kscale)
 
 
 def fold_block_shared(wf, wg, wh, bg, bh, rstd_c, mu_s, rstd_s, dtype: torch.dtype, kscale: float = LOG2E):
     """``fold_block`` for B content frames (rstd_c [B][C]) against ONE style (mu_s, rstd_s [1][C]): wq
     [B][H][64][64] per frame; wkv [1][H][128][64], bkv and v_mu [1][C] of the style.  The existing entry with
     the style statistics repeated (B x C floats): no kernel of its own, so the bits are fold_block's."""
-    B, C = rstd_c.shape
-    if mu_s.shape != (1, C) or rstd_s.shape != (1, C):
-        raise ValueError(f"fold_block_shared: the style statistics must be [1][{C}], got {tuple(mu_s.shape)}")
-    wq, wkv, bkv, v_mu = fold_block(wf, wg, wh, bg, bh, rstd_c, mu_s.expand(B, C).contiguous(),
-                                    rstd_s.expand(B, C).contiguous(), dtype, kscale)
-    return wq, wkv[:1], bkv, v_mu[:1]
+    return _fold_block_shared("fold_block_shared", fold_block, wf, wg, wh, bg, bh, rstd_c, mu_s, rstd_s, dtype,
+                              kscale)
+
+
+def fold_block_hd(wf, wg, wh, bg, bh, rstd_c, mu_s, rstd_s, dtype: torch.dtype, kscale: float = LOG2E):
+    """``mhada_fold_block_hd``: fold_block for W* [H][D][D], D = 32 | 128."""
+    return _fold_block("fold_block_hd", True, wf, wg, wh, bg, bh, rstd_c, mu_s, rstd_s, dtype, kscale)
+
+
+def fold_block_hd_shared(wf, wg, wh, bg, bh, rstd_c, mu_s, rstd_s, dtype: torch.dtype, kscale: float = LOG2E):
+    """``fold_block_hd`` for B content frames (rstd_c [B][C]) against ONE style (mu_s, rstd_s [1][C]): wq
+    [B][H][D][D] per frame; wkv [1][H][2D][D], bkv and v_mu [1][C] of the style.  As ``fold_block_shared``."""
+    return _fold_block_shared("fold_block_hd_shared", fold_block_hd, wf, wg, wh, bg, bh, rstd_c, mu_s, rstd_s,
+                              dtype, kscale)
 
 
 def transpose_v(kv: torch.Tensor) -> torch.Tensor:
@@ -1004,30 +1030,6 @@ def cosine_moments(kv: torch.Tensor, vt: torch.Tensor) -> torch.Tensor:
     return mom
 
 
-def cosine_attn(q, mom, fcs, fcs_mu, fcs_rstd, v_mu) -> torch.Tensor:
-    """``mhada_cosine_attn``: mhada_attn's output for the cosine activation from normalised q and
-    the style moments of cosine_moments."""
-    _need_gpu(q, mom, fcs, fcs_mu, fcs_rstd, v_mu)
-    B, H, Nc, _ = q.shape
-    if mom.shape != (B, H, 65, 132) or mom.dtype != torch.float32:
-        raise ValueError(f"cosine_attn: mom {tuple(mom.shape)} does not match q {tuple(q.shape)}")
-    out = torch.empty(B, Nc, H * 64, device=q.device, dtype=q.dtype)
-    _call("mhada_cosine_attn", q, q.data_ptr(), mom.data_ptr(), fcs.data_ptr(), fcs_mu.data_ptr(),
-          fcs_rstd.data_ptr(), v_mu.data_ptr(), out.data_ptr(), dt_code(q.dtype), B, H, Nc)
-    return out
-
-
-def mhada_attn(q, kv, vt, fcs, fcs_mu, fcs_rstd, v_mu, activation: int) -> torch.Tensor:
-    _need_gpu(q, kv, vt, fcs, fcs_mu, fcs_rstd, v_mu)
-    B, H, Nc, _ = q.shape
-    Ns = kv.shape[2]
-    out = torch.empty(B, Nc, H * 64, device=q.device, dtype=q.dtype)
-    _call("mhada_attn", q, q.data_ptr(), kv.data_ptr(), _ptr(vt), fcs.data_ptr(), fcs_mu.data_ptr(),
-                                fcs_rstd.data_ptr(), v_mu.data_ptr(), out.data_ptr(), dt_code(q.dtype), B, H, Nc,
-                                Ns, activation)
-    return out
-
-
 def _shared_style(what: str, q, fcs, fcs_mu, fcs_rstd, v_mu) -> None:
     B, H, Nc, D = q.shape
     C = H * 64
@@ -1041,69 +1043,61 @@ def _shared_style(what: str, q, fcs, fcs_mu, fcs_rstd, v_mu) -> None:
             raise ValueError(f"{what}: fcs, its statistics and v_mu must be contiguous float32")
 
 
-def mhada_attn_shared(q, kv, vt, fcs, fcs_mu, fcs_rstd, v_mu) -> torch.Tensor:
-    """``mhada_attn_shared``: the softmax ``mhada_attn`` of B frames (q [B][H][Nc][64], fcs and statistics
-    per frame) against ONE style (kv [1][H][Ns][128], vt [1][H][128][ceil64(Ns)], v_mu [1][C]); every frame
-    gets the bits of ``mhada_attn`` with the style operands repeated B times.  fp32 or bf16."""
-    _need_gpu(q, kv, vt, fcs, fcs_mu, fcs_rstd, v_mu)
-    _shared_style("mhada_attn_shared", q, fcs, fcs_mu, fcs_rstd, v_mu)
+def _cosine_attn(what: str, shared: bool, q, mom, fcs, fcs_mu, fcs_rstd, v_mu):
+    _need_gpu(q, mom, fcs, fcs_mu, fcs_rstd, v_mu)
+    if shared:
+        _shared_style(what, q, fcs, fcs_mu, fcs_rstd, v_mu)
     B, H, Nc, _ = q.shape
-    Ns = kv.shape[2]
-    ldt = (Ns + 63) // 64 * 64
-    if kv.shape != (1, H, Ns, 128) or vt.shape != (1, H, 128, ldt) or kv.dtype != q.dtype or vt.dtype != q.dtype \
-            or not kv.is_contiguous() or not vt.is_contiguous():
-        raise ValueError(f"mhada_attn_shared: kv / vt must be one style's contiguous [1][{H}][Ns][128] / "
-                         f"[1][{H}][128][{ldt}] of q's dtype, got {tuple(kv.shape)} / {tuple(vt.shape)}")
+    Bs = 1 if shared else B
+    if mom.shape != (Bs, H, 65, 132) or mom.dtype != torch.float32 or (shared and not mom.is_contiguous()):
+        raise ValueError(f"{what}: mom must be fp32 [{Bs}][{H}][65][132]{' of one style, contiguous' if shared else ''}"
+                         f", got {tuple(mom.shape)} {mom.dtype}")
     out = torch.empty(B, Nc, H * 64, device=q.device, dtype=q.dtype)
-    _call("mhada_attn_shared", q, q.data_ptr(), kv.data_ptr(), vt.data_ptr(), fcs.data_ptr(), fcs_mu.data_ptr(),
-          fcs_rstd.data_ptr(), v_mu.data_ptr(), out.data_ptr(), dt_code(q.dtype), B, H, Nc, Ns, _lib.ACT_SOFTMAX)
+    _call("mhada_" + what, q, q.data_ptr(), mom.data_ptr(), fcs.data_ptr(), fcs_mu.data_ptr(),
+          fcs_rstd.data_ptr(), v_mu.data_ptr(), out.data_ptr(), dt_code(q.dtype), B, H, Nc)
     return out
+
+
+def cosine_attn(q, mom, fcs, fcs_mu, fcs_rstd, v_mu) -> torch.Tensor:
+    """``mhada_cosine_attn``: mhada_attn's output for the cosine activation from normalised q and
+    the style moments of cosine_moments."""
+    return _cosine_attn("cosine_attn", False, q, mom, fcs, fcs_mu, fcs_rstd, v_mu)
 
 
 def cosine_attn_shared(q, mom, fcs, fcs_mu, fcs_rstd, v_mu) -> torch.Tensor:
     """``mhada_cosine_attn_shared``: ``cosine_attn`` of B frames (normalised q [B][H][Nc][64], fcs and statistics
     per frame) against ONE style (mom [1][H][65][132] of cosine_moments, v_mu [1][C]); every frame gets the bits
     of ``cosine_attn`` with mom and v_mu repeated B times.  fp32 or bf16."""
-    _need_gpu(q, mom, fcs, fcs_mu, fcs_rstd, v_mu)
-    _shared_style("cosine_attn_shared", q, fcs, fcs_mu, fcs_rstd, v_mu)
+    return _cosine_attn("cosine_attn_shared", True, q, mom, fcs, fcs_mu, fcs_rstd, v_mu)
+
+
+def _mhada_attn(what: str, shared: bool, q, kv, vt, fcs, fcs_mu, fcs_rstd, v_mu, activation: int):
+    """mhada_attn (no checks of its own; vt may be None) and mhada_attn_shared (one style's kv / vt, checked)."""
+    _need_gpu(q, kv, vt, fcs, fcs_mu, fcs_rstd, v_mu)
+    if shared:
+        _shared_style(what, q, fcs, fcs_mu, fcs_rstd, v_mu)
     B, H, Nc, _ = q.shape
-    if mom.shape != (1, H, 65, 132) or mom.dtype != torch.float32 or not mom.is_contiguous():
-        raise ValueError(f"cosine_attn_shared: mom must be one style's contiguous fp32 [1][{H}][65][132], got "
-                         f"{tuple(mom.shape)} {mom.dtype}")
+    Ns = kv.shape[2]
+    ldt = (Ns + 63) // 64 * 64
+    if shared and (kv.shape != (1, H, Ns, 128) or vt.shape != (1, H, 128, ldt) or kv.dtype != q.dtype
+                   or vt.dtype != q.dtype or not kv.is_contiguous() or not vt.is_contiguous()):
+        raise ValueError(f"{what}: kv / vt must be one style's contiguous [1][{H}][Ns][128] / "
+                         f"[1][{H}][128][{ldt}] of q's dtype, got {tuple(kv.shape)} / {tuple(vt.shape)}")
     out = torch.empty(B, Nc, H * 64, device=q.device, dtype=q.dtype)
-    _call("mhada_cosine_attn_shared", q, q.data_ptr(), mom.data_ptr(), fcs.data_ptr(), fcs_mu.data_ptr(),
-          fcs_rstd.data_ptr(), v_mu.data_ptr(), out.data_ptr(), dt_code(q.dtype), B, H, Nc)
+    _call(what, q, q.data_ptr(), kv.data_ptr(), _ptr(vt), fcs.data_ptr(), fcs_mu.data_ptr(), fcs_rstd.data_ptr(),
+          v_mu.data_ptr(), out.data_ptr(), dt_code(q.dtype), B, H, Nc, Ns, activation)
     return out
 
 
-HD_WIDTHS = (32, 128)  # head widths of the *_hd entry points (csrc/attn_hd.hip); 64 has its own kernels
+def mhada_attn(q, kv, vt, fcs, fcs_mu, fcs_rstd, v_mu, activation: int) -> torch.Tensor:
+    return _mhada_attn("mhada_attn", False, q, kv, vt, fcs, fcs_mu, fcs_rstd, v_mu, activation)
 
 
-def _hd_width(what: str, D: int) -> None:
-    if D not in HD_WIDTHS:
-        raise ValueError(f"{what}: head width must be 32 or 128 (64 has its own entry point), got {D}")
-
-
-def fold_block_hd(wf, wg, wh, bg, bh, rstd_c, mu_s, rstd_s, dtype: torch.dtype, kscale: float = LOG2E):
-    """``mhada_fold_block_hd``: fold_block for W* [H][D][D], D = 32 | 128."""
-    _need_gpu(wf, wg, wh, bg, bh, rstd_c, mu_s, rstd_s)
-    B, C = rstd_c.shape
-    H, D = wf.shape[0], wf.shape[1]
-    _hd_width("fold_block_hd", D)
-    for t, shape in ((wf, (H, D, D)), (wg, (H, D, D)), (wh, (H, D, D)), (bg, (H, D)), (bh, (H, D)),
-                     (rstd_c, (B, H * D)), (mu_s, (B, H * D)), (rstd_s, (B, H * D))):
-        if tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous():
-            raise ValueError(f"fold_block_hd: needs contiguous fp32 {shape}, got {tuple(t.shape)} {t.dtype}")
-    dt_code(dtype)
-    dev = wf.device
-    wq = torch.empty(B, H, D, D, device=dev, dtype=dtype)
-    wkv = torch.empty(B, H, 2 * D, D, device=dev, dtype=dtype)
-    bkv = torch.empty(H, 2 * D, device=dev, dtype=torch.float32)
-    v_mu = torch.empty(B, C, device=dev, dtype=torch.float32)
-    _call("mhada_fold_block_hd", wf, wf.data_ptr(), wg.data_ptr(), wh.data_ptr(), bg.data_ptr(), bh.data_ptr(),
-          rstd_c.data_ptr(), mu_s.data_ptr(), rstd_s.data_ptr(), wq.data_ptr(), wkv.data_ptr(), bkv.data_ptr(),
-          v_mu.data_ptr(), kscale, dt_code(dtype), B, H, D)
-    return wq, wkv, bkv, v_mu
+def mhada_attn_shared(q, kv, vt, fcs, fcs_mu, fcs_rstd, v_mu) -> torch.Tensor:
+    """``mhada_attn_shared``: the softmax ``mhada_attn`` of B frames (q [B][H][Nc][64], fcs and statistics
+    per frame) against ONE style (kv [1][H][Ns][128], vt [1][H][128][ceil64(Ns)], v_mu [1][C]); every frame
+    gets the bits of ``mhada_attn`` with the style operands repeated B times.  fp32 or bf16."""
+    return _mhada_attn("mhada_attn_shared", True, q, kv, vt, fcs, fcs_mu, fcs_rstd, v_mu, _lib.ACT_SOFTMAX)
 
 
 def cosine_prep_hd(q: Optional[torch.Tensor], kv: Optional[torch.Tensor]) -> None:
@@ -1129,67 +1123,43 @@ def cosine_prep_hd(q: Optional[torch.Tensor], kv: Optional[torch.Tensor]) -> Non
           D, Nc, Ns)
 
 
-def attn_hd(q, kv, fcs, fcs_mu, fcs_rstd, v_mu, activation: int) -> torch.Tensor:
-    """``mhada_attn_hd``: the fused MHAda attention at D = 32 | 128 from q [B][H][Nc][D] and kv
-    [B][H][Ns][2D] (K | V'); out [B][Nc][D H] in q's dtype."""
+def _attn_hd(what: str, shared: bool, q, kv, fcs, fcs_mu, fcs_rstd, v_mu, activation: int):
+    """attn_hd and attn_hd_shared (kv and v_mu with a leading batch of 1); entry point "mhada_" + what."""
     _need_gpu(q, kv, fcs, fcs_mu, fcs_rstd, v_mu)
+    bs = "1" if shared else "B"
     if q.dim() != 4 or kv.dim() != 4:
-        raise ValueError(f"attn_hd: needs q [B][H][Nc][D] and kv [B][H][Ns][2D], got {tuple(q.shape)} / {tuple(kv.shape)}")
+        raise ValueError(f"{what}: needs q [B][H][Nc][D] and kv [{bs}][H][Ns][2D], got {tuple(q.shape)} / "
+                         f"{tuple(kv.shape)}")
     B, H, Nc, D = q.shape
     Ns = kv.shape[2]
-    _hd_width("attn_hd", D)
+    _hd_width(what, D)
     C = H * D
-    if kv.shape != (B, H, Ns, 2 * D) or kv.dtype != q.dtype or not q.is_contiguous() or not kv.is_contiguous():
-        raise ValueError(f"attn_hd: needs contiguous q [B][H][Nc][{D}] and kv [B][H][Ns][{2 * D}] of one dtype, got "
+    Bs = 1 if shared else B
+    if kv.shape != (Bs, H, Ns, 2 * D) or kv.dtype != q.dtype or not q.is_contiguous() or not kv.is_contiguous():
+        raise ValueError(f"{what}: needs contiguous q [B][H][Nc][{D}] and kv [{bs}][H][Ns][{2 * D}] of one dtype, got "
                          f"{tuple(q.shape)} {q.dtype} / {tuple(kv.shape)} {kv.dtype}")
     if Nc <= 0 or Ns <= 0:
-        raise ValueError(f"attn_hd: needs Nc > 0 and Ns > 0, got {Nc} / {Ns}")
-    for t, shape in ((fcs, (B, Nc, C)), (fcs_mu, (B, C)), (fcs_rstd, (B, C)), (v_mu, (B, C))):
+        raise ValueError(f"{what}: needs Nc > 0 and Ns > 0, got {Nc} / {Ns}")
+    for t, shape in ((fcs, (B, Nc, C)), (fcs_mu, (B, C)), (fcs_rstd, (B, C)), (v_mu, (Bs, C))):
         if tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous():
-            raise ValueError(f"attn_hd: needs contiguous fp32 {shape}, got {tuple(t.shape)} {t.dtype}")
+            raise ValueError(f"{what}: needs contiguous fp32 {shape}, got {tuple(t.shape)} {t.dtype}")
     out = torch.empty(B, Nc, C, device=q.device, dtype=q.dtype)
-    _call("mhada_attn_hd", q, q.data_ptr(), kv.data_ptr(), fcs.data_ptr(), fcs_mu.data_ptr(), fcs_rstd.data_ptr(),
+    _call("mhada_" + what, q, q.data_ptr(), kv.data_ptr(), fcs.data_ptr(), fcs_mu.data_ptr(), fcs_rstd.data_ptr(),
           v_mu.data_ptr(), out.data_ptr(), dt_code(q.dtype), B, H, D, Nc, Ns, activation)
     return out
 
 
-def fold_block_hd_shared(wf, wg, wh, bg, bh, rstd_c, mu_s, rstd_s, dtype: torch.dtype, kscale: float = LOG2E):
-    """``fold_block_hd`` for B content frames (rstd_c [B][C]) against ONE style (mu_s, rstd_s [1][C]): wq
-    [B][H][D][D] per frame; wkv [1][H][2D][D], bkv and v_mu [1][C] of the style.  The existing entry with the
-    style statistics repeated, as ``fold_block_shared``: no kernel of its own, so the bits are fold_block_hd's."""
-    B, C = rstd_c.shape
-    if mu_s.shape != (1, C) or rstd_s.shape != (1, C):
-        raise ValueError(f"fold_block_hd_shared: the style statistics must be [1][{C}], got {tuple(mu_s.shape)} / "
-                         f"{tuple(rstd_s.shape)}")
-    wq, wkv, bkv, v_mu = fold_block_hd(wf, wg, wh, bg, bh, rstd_c, mu_s.expand(B, C).contiguous(),
-                                       rstd_s.expand(B, C).contiguous(), dtype, kscale)
-    return wq, wkv[:1], bkv, v_mu[:1]
+def attn_hd(q, kv, fcs, fcs_mu, fcs_rstd, v_mu, activation: int) -> torch.Tensor:
+    """``mhada_attn_hd``: the fused MHAda attention at D = 32 | 128 from q [B][H][Nc][D] and kv
+    [B][H][Ns][2D] (K | V'); out [B][Nc][D H] in q's dtype."""
+    return _attn_hd("attn_hd", False, q, kv, fcs, fcs_mu, fcs_rstd, v_mu, activation)
 
 
 def attn_hd_shared(q, kv, fcs, fcs_mu, fcs_rstd, v_mu, activation: int) -> torch.Tensor:
     """``mhada_attn_hd_shared``: ``attn_hd`` of B frames (q [B][H][Nc][D], fcs and statistics per frame) against
     ONE style (kv [1][H][Ns][2D], v_mu [1][C]); every frame gets the bits of ``attn_hd`` with kv and v_mu repeated
     B times.  D = 32 | 128, both activations, fp32 or bf16."""
-    _need_gpu(q, kv, fcs, fcs_mu, fcs_rstd, v_mu)
-    if q.dim() != 4 or kv.dim() != 4:
-        raise ValueError(f"attn_hd_shared: needs q [B][H][Nc][D] and kv [1][H][Ns][2D], got {tuple(q.shape)} / "
-                         f"{tuple(kv.shape)}")
-    B, H, Nc, D = q.shape
-    Ns = kv.shape[2]
-    _hd_width("attn_hd_shared", D)
-    C = H * D
-    if kv.shape != (1, H, Ns, 2 * D) or kv.dtype != q.dtype or not q.is_contiguous() or not kv.is_contiguous():
-        raise ValueError(f"attn_hd_shared: needs contiguous q [B][H][Nc][{D}] and one style's kv [1][H][Ns][{2 * D}] of "
-                         f"one dtype, got {tuple(q.shape)} {q.dtype} / {tuple(kv.shape)} {kv.dtype}")
-    if Nc <= 0 or Ns <= 0:
-        raise ValueError(f"attn_hd_shared: needs Nc > 0 and Ns > 0, got {Nc} / {Ns}")
-    for t, shape in ((fcs, (B, Nc, C)), (fcs_mu, (B, C)), (fcs_rstd, (B, C)), (v_mu, (1, C))):
-        if tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous():
-            raise ValueError(f"attn_hd_shared: needs contiguous fp32 {shape}, got {tuple(t.shape)} {t.dtype}")
-    out = torch.empty(B, Nc, C, device=q.device, dtype=q.dtype)
-    _call("mhada_attn_hd_shared", q, q.data_ptr(), kv.data_ptr(), fcs.data_ptr(), fcs_mu.data_ptr(),
-          fcs_rstd.data_ptr(), v_mu.data_ptr(), out.data_ptr(), dt_code(q.dtype), B, H, D, Nc, Ns, activation)
-    return out
+    return _attn_hd("attn_hd_shared", True, q, kv, fcs, fcs_mu, fcs_rstd, v_mu, activation)
 
 
 WIDE_WIDTH = 512  # the head width of mhada_attn_wide (csrc/attn_wide.hip): one head over all channels
@@ -1269,71 +1239,52 @@ def kv_proj_split3(fs: torch.Tensor, mu_s: torch.Tensor, wkv: torch.Tensor, bkv:
     return img
 
 
+def _attn_split3(what: str, shared: bool, planes: bool, q, img, Ns: int, fcs, fcs_mu, fcs_rstd, v_mu):
+    """The four attn_split3* ops (entry point "mhada_" + what): the output as fp32 rows [B][Nc][64 H] or
+    (``planes``) its three bf16 planes [3][B * Nc][64 H]; the style's plane image img at batch B or (``shared``,
+    with the shared-style operand checks) at batch 1."""
+    _need_gpu(q, img, fcs, fcs_mu, fcs_rstd, v_mu)
+    if shared:
+        _shared_style(what, q, fcs, fcs_mu, fcs_rstd, v_mu)
+    B, H, Nc, _ = q.shape
+    ldt = (Ns + 63) // 64 * 64
+    if shared and (q.dtype != torch.float32 or img.dtype != torch.bfloat16 or img.shape != (1, H, 576 * ldt)
+                   or not img.is_contiguous()):
+        raise ValueError(f"{what}: q must be fp32 and img one style's bf16 [1][{H}][576*{ldt}], got "
+                         f"{q.dtype} / {tuple(img.shape)}")
+    if not shared and (q.dtype != torch.float32 or not q.is_contiguous() or img.dtype != torch.bfloat16
+                       or img.shape != (B, H, 576 * ldt)):
+        raise ValueError(f"{what}: q must be contiguous fp32 and img bf16 [B][H][576*{ldt}], got "
+                         f"{q.dtype} / {tuple(img.shape)}")
+    out = torch.empty(3, B * Nc, H * 64, device=q.device, dtype=torch.bfloat16) if planes else \
+        torch.empty(B, Nc, H * 64, device=q.device, dtype=torch.float32)
+    _call("mhada_" + what, q, q.data_ptr(), img.data_ptr(), fcs.data_ptr(), fcs_mu.data_ptr(),
+          fcs_rstd.data_ptr(), v_mu.data_ptr(), out.data_ptr(), B, H, Nc, Ns)
+    return out
+
+
 def attn_split3(q, img, Ns: int, fcs, fcs_mu, fcs_rstd, v_mu) -> torch.Tensor:
     """``mhada_attn_split3``: mhada_attn's fp32 softmax output from fp32 q [B][H][Nc][64] and the
     ``split3_kv`` plane image of Ns keys."""
-    _need_gpu(q, img, fcs, fcs_mu, fcs_rstd, v_mu)
-    B, H, Nc, _ = q.shape
-    ldt = (Ns + 63) // 64 * 64
-    if q.dtype != torch.float32 or not q.is_contiguous() or img.dtype != torch.bfloat16 \
-            or img.shape != (B, H, 576 * ldt):
-        raise ValueError(f"attn_split3: q must be contiguous fp32 and img bf16 [B][H][576*{ldt}], got "
-                         f"{q.dtype} / {tuple(img.shape)}")
-    out = torch.empty(B, Nc, H * 64, device=q.device, dtype=torch.float32)
-    _call("mhada_attn_split3", q, q.data_ptr(), img.data_ptr(), fcs.data_ptr(), fcs_mu.data_ptr(),
-          fcs_rstd.data_ptr(), v_mu.data_ptr(), out.data_ptr(), B, H, Nc, Ns)
-    return out
+    return _attn_split3("attn_split3", False, False, q, img, Ns, fcs, fcs_mu, fcs_rstd, v_mu)
 
 
 def attn_split3_planes(q, img, Ns: int, fcs, fcs_mu, fcs_rstd, v_mu) -> torch.Tensor:
     """``mhada_attn_split3_planes``: ``attn_split3``'s output as its three bf16 planes [3][B * Nc][64 H]
     (bit-identical to ``split3_rows`` of it), the A operand of the out_conv ``linear_split3``."""
-    _need_gpu(q, img, fcs, fcs_mu, fcs_rstd, v_mu)
-    B, H, Nc, _ = q.shape
-    ldt = (Ns + 63) // 64 * 64
-    if q.dtype != torch.float32 or not q.is_contiguous() or img.dtype != torch.bfloat16 \
-            or img.shape != (B, H, 576 * ldt):
-        raise ValueError(f"attn_split3_planes: q must be contiguous fp32 and img bf16 [B][H][576*{ldt}], got "
-                         f"{q.dtype} / {tuple(img.shape)}")
-    planes = torch.empty(3, B * Nc, H * 64, device=q.device, dtype=torch.bfloat16)
-    _call("mhada_attn_split3_planes", q, q.data_ptr(), img.data_ptr(), fcs.data_ptr(), fcs_mu.data_ptr(),
-          fcs_rstd.data_ptr(), v_mu.data_ptr(), planes.data_ptr(), B, H, Nc, Ns)
-    return planes
-
-
-def _shared_img(what: str, q, img, Ns: int) -> None:
-    H = q.shape[1]
-    ldt = (Ns + 63) // 64 * 64
-    if q.dtype != torch.float32 or img.dtype != torch.bfloat16 or img.shape != (1, H, 576 * ldt) \
-            or not img.is_contiguous():
-        raise ValueError(f"{what}: q must be fp32 and img one style's bf16 [1][{H}][576*{ldt}], got "
-                         f"{q.dtype} / {tuple(img.shape)}")
+    return _attn_split3("attn_split3_planes", False, True, q, img, Ns, fcs, fcs_mu, fcs_rstd, v_mu)
 
 
 def attn_split3_shared(q, img, Ns: int, fcs, fcs_mu, fcs_rstd, v_mu) -> torch.Tensor:
     """``mhada_attn_split3_shared``: ``attn_split3`` of B frames against ONE style's plane image
     [1][H][576 ceil64(Ns)] and v_mu [1][C]; every frame gets ``attn_split3``'s bits."""
-    _need_gpu(q, img, fcs, fcs_mu, fcs_rstd, v_mu)
-    _shared_style("attn_split3_shared", q, fcs, fcs_mu, fcs_rstd, v_mu)
-    _shared_img("attn_split3_shared", q, img, Ns)
-    B, H, Nc, _ = q.shape
-    out = torch.empty(B, Nc, H * 64, device=q.device, dtype=torch.float32)
-    _call("mhada_attn_split3_shared", q, q.data_ptr(), img.data_ptr(), fcs.data_ptr(), fcs_mu.data_ptr(),
-          fcs_rstd.data_ptr(), v_mu.data_ptr(), out.data_ptr(), B, H, Nc, Ns)
-    return out
+    return _attn_split3("attn_split3_shared", True, False, q, img, Ns, fcs, fcs_mu, fcs_rstd, v_mu)
 
 
 def attn_split3_planes_shared(q, img, Ns: int, fcs, fcs_mu, fcs_rstd, v_mu) -> torch.Tensor:
     """``mhada_attn_split3_planes_shared``: ``attn_split3_planes`` of B frames against ONE style; planes
     [3][B * Nc][64 H]."""
-    _need_gpu(q, img, fcs, fcs_mu, fcs_rstd, v_mu)
-    _shared_style("attn_split3_planes_shared", q, fcs, fcs_mu, fcs_rstd, v_mu)
-    _shared_img("attn_split3_planes_shared", q, img, Ns)
-    B, H, Nc, _ = q.shape
-    planes = torch.empty(3, B * Nc, H * 64, device=q.device, dtype=torch.bfloat16)
-    _call("mhada_attn_split3_planes_shared", q, q.data_ptr(), img.data_ptr(), fcs.data_ptr(), fcs_mu.data_ptr(),
-          fcs_rstd.data_ptr(), v_mu.data_ptr(), planes.data_ptr(), B, H, Nc, Ns)
-    return planes
+    return _attn_split3("attn_split3_planes_shared", True, True, q, img, Ns, fcs, fcs_mu, fcs_rstd, v_mu)
 
 
 def _rows64(*ts: torch.Tensor) -> None:
@@ -1343,18 +1294,44 @@ def _rows64(*ts: torch.Tensor) -> None:
             raise ValueError("training attention operands must be contiguous float32")
 
 
+def _train_hd_width(what: str, t: torch.Tensor) -> int:
+    D = t.shape[-1] if t.dim() == 3 else -1
+    if D not in (32, 128):
+        raise ValueError(f"{what}: rows of 32 or 128 floats (64: the op without _hd), got {tuple(t.shape)}")
+    return D
+
+
+def _train_shapes(what: str, D: Optional[int], q, k, v, *others, lax: str = ""):
+    """The operand checks of every training-attention op -> (BH, Nc, Ns, D): contiguous fp32 device tensors, q (BH,
+    Nc, D), k and v (BH, Ns, D) with Ns > 0, and ``others``, (tensor, kind) pairs in the op's argument order: kind
+    "q" is shaped like q (x), "row" (BH, Nc) (lse, dd), "wide" (BH, Nc, 2D) ([M' | E2'] and its gradient).
+    D None: 32 | 128, read from q (the _hd ops).  ``lax``: the 64-wide fp32 ops check what they always have and
+    no more — "fwd" takes k of any rank and Ns = 0, "bwd" also leaves q's width unchecked."""
+    _rows64(q, k, v, *(t for t, _ in others))
+    if D is None:
+        D = _train_hd_width(what, q)
+    BH, Nc, d = q.shape if q.dim() == 3 else (0, 0, -1)
+    Ns = k.shape[1] if k.dim() == 3 or (lax and q.dim() == 3) else -1
+    want = {"q": tuple(q.shape), "row": (BH, Nc), "wide": (BH, Nc, 2 * D)}
+    if q.dim() != 3 or (d != D and lax != "bwd") or k.shape != (BH, Ns, D) or v.shape != k.shape \
+            or (Ns <= 0 and not lax) or any(tuple(t.shape) != want[kind] for t, kind in others):
+        raise ValueError(f"{what}: bad shapes q{tuple(q.shape)} k{tuple(k.shape)} v{tuple(v.shape)}, others "
+                         + " ".join(str(tuple(t.shape)) for t, _ in others))
+    return BH, Nc, Ns, D
+
+
+def _train_fwd_out(q: torch.Tensor, D: int):
+    """The forward's outputs: out' like q, [M' | E2'] (BH, Nc, 2D), lse2 (BH, Nc)."""
+    BH, Nc, _ = q.shape
+    return (torch.empty_like(q), torch.empty(BH, Nc, 2 * D, device=q.device, dtype=torch.float32),
+            torch.empty(BH, Nc, device=q.device, dtype=torch.float32))
+
+
 def attn_train_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, x: torch.Tensor):
     """``mhada_attn_train_fwd``: q, x (BH, Nc, 64); k, v (BH, Ns, 64) with v centred.
     Returns out' (BH, Nc, 64), [M' | E2'] (BH, Nc, 128), lse2 (BH, Nc)."""
-    _rows64(q, k, v, x)
-    BH, Nc, d = q.shape
-    Ns = k.shape[1]
-    if d != 64 or k.shape != (BH, Ns, 64) or v.shape != k.shape or x.shape != q.shape:
-        raise ValueError(f"attn_train_fwd: bad shapes q{tuple(q.shape)} k{tuple(k.shape)} v{tuple(v.shape)} "
-                         f"x{tuple(x.shape)}")
-    out = torch.empty_like(q)
-    mo = torch.empty(BH, Nc, 128, device=q.device, dtype=torch.float32)
-    lse = torch.empty(BH, Nc, device=q.device, dtype=torch.float32)
+    BH, Nc, Ns, _ = _train_shapes("attn_train_fwd", 64, q, k, v, (x, "q"), lax="fwd")
+    out, mo, lse = _train_fwd_out(q, 64)
     if TRAIN_FWD_S3:
         # SPLIT3 products on the bf16 MFMA (csrc/attn_split3.hip) over a bf16 plane image of k, v
         # (workspace, freed after)
@@ -1418,12 +1395,8 @@ def attn_train_bwd(q, k, v, lse, dmo, dd, spill: Optional[bool] = None):
     """``mhada_attn_train_bwd``: returns dq (BH, Nc, 64), dk, dv (BH, Ns, 64).  With the dS spill
     (default when ``ds_spill_eligible``): ``mhada_attn_train_dkv`` writes dS and dQ = dS K runs as
     one batched GEMM (896 instead of 1280 FLOP per query-key-head pair)."""
-    _rows64(q, k, v, lse, dmo, dd)
-    BH, Nc, _ = q.shape
-    Ns = k.shape[1]
-    if lse.shape != (BH, Nc) or dmo.shape != (BH, Nc, 128) or dd.shape != (BH, Nc) or k.shape != (BH, Ns, 64) \
-            or v.shape != k.shape:
-        raise ValueError("attn_train_bwd: bad shapes")
+    BH, Nc, Ns, _ = _train_shapes("attn_train_bwd", 64, q, k, v, (lse, "row"), (dmo, "wide"), (dd, "row"),
+                                   lax="bwd")
     auto = spill is None
     if auto:
         spill = ds_spill_eligible(BH, Nc, Ns)
@@ -1468,12 +1441,8 @@ def attn_train_dq(q, k, v, lse, dmo, dd):
     """``mhada_attn_train_dq``: the dq (BH, Nc, 64) of ``attn_train_bwd(..., spill=False)`` alone — the
     query-stationary recompute kernel, bit-identical to that call's dq; dk and dv are not computed
     (a feature inversion: the key / value side carries no gradient)."""
-    _rows64(q, k, v, lse, dmo, dd)
-    BH, Nc, _ = q.shape
-    Ns = k.shape[1]
-    if lse.shape != (BH, Nc) or dmo.shape != (BH, Nc, 128) or dd.shape != (BH, Nc) or k.shape != (BH, Ns, 64) \
-            or v.shape != k.shape:
-        raise ValueError("attn_train_dq: bad shapes")
+    BH, Nc, Ns, _ = _train_shapes("attn_train_dq", 64, q, k, v, (lse, "row"), (dmo, "wide"), (dd, "row"),
+                                   lax="bwd")
     DQ_ONLY_COUNTS["dq_only"] += 1
     dq = torch.empty_like(q)
     _call("mhada_attn_train_dq", q, q.data_ptr(), k.data_ptr(), v.data_ptr(), lse.data_ptr(), dmo.data_ptr(),
@@ -1481,27 +1450,12 @@ def attn_train_dq(q, k, v, lse, dmo, dd):
     return dq
 
 
-def _train_hd_width(what: str, t: torch.Tensor) -> int:
-    D = t.shape[-1] if t.dim() == 3 else -1
-    if D not in (32, 128):
-        raise ValueError(f"{what}: rows of 32 or 128 floats (64: the op without _hd), got {tuple(t.shape)}")
-    return D
-
-
 def attn_train_fwd_hd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, x: torch.Tensor):
     """``mhada_attn_train_fwd_hd``: ``attn_train_fwd`` at head width D = 32 | 128 (csrc/attn_train.hip):
     q, x (BH, Nc, D); k, v (BH, Ns, D) with v centred.  Returns out' (BH, Nc, D), [M' | E2'] (BH, Nc, 2D),
     lse2 (BH, Nc).  One fp32-MFMA kernel; the TRAIN_FWD_* knobs are 64-wide only."""
-    _rows64(q, k, v, x)
-    D = _train_hd_width("attn_train_fwd_hd", q)
-    BH, Nc, _ = q.shape
-    Ns = k.shape[1] if k.dim() == 3 else -1
-    if k.shape != (BH, Ns, D) or v.shape != k.shape or x.shape != q.shape or Ns <= 0:
-        raise ValueError(f"attn_train_fwd_hd: bad shapes q{tuple(q.shape)} k{tuple(k.shape)} v{tuple(v.shape)} "
-                         f"x{tuple(x.shape)}")
-    out = torch.empty_like(q)
-    mo = torch.empty(BH, Nc, 2 * D, device=q.device, dtype=torch.float32)
-    lse = torch.empty(BH, Nc, device=q.device, dtype=torch.float32)
+    BH, Nc, Ns, D = _train_shapes("attn_train_fwd_hd", None, q, k, v, (x, "q"))
+    out, mo, lse = _train_fwd_out(q, D)
     _call("mhada_attn_train_fwd_hd", q, q.data_ptr(), k.data_ptr(), v.data_ptr(), x.data_ptr(), out.data_ptr(),
           mo.data_ptr(), lse.data_ptr(), BH, D, Nc, Ns)
     return out, mo, lse
@@ -1511,13 +1465,7 @@ def attn_train_bwd_hd(q, k, v, lse, dmo, dd):
     """``mhada_attn_train_bwd_hd``: ``attn_train_bwd`` at head width D = 32 | 128: returns dq (BH, Nc, D),
     dk, dv (BH, Ns, D).  Always the recompute backward (no dS spill at these widths, no workspace);
     BWD_PATH_COUNTS counts the 64-wide paths only."""
-    _rows64(q, k, v, lse, dmo, dd)
-    D = _train_hd_width("attn_train_bwd_hd", q)
-    BH, Nc, _ = q.shape
-    Ns = k.shape[1] if k.dim() == 3 else -1
-    if lse.shape != (BH, Nc) or dmo.shape != (BH, Nc, 2 * D) or dd.shape != (BH, Nc) or k.shape != (BH, Ns, D) \
-            or v.shape != k.shape or Ns <= 0:
-        raise ValueError("attn_train_bwd_hd: bad shapes")
+    BH, Nc, Ns, D = _train_shapes("attn_train_bwd_hd", None, q, k, v, (lse, "row"), (dmo, "wide"), (dd, "row"))
     dq = torch.empty_like(q)
     dk = torch.empty_like(k)
     dv = torch.empty_like(v)
@@ -1529,13 +1477,7 @@ def attn_train_bwd_hd(q, k, v, lse, dmo, dd):
 def attn_train_dq_hd(q, k, v, lse, dmo, dd):
     """``mhada_attn_train_dq_hd``: ``attn_train_dq`` at head width D = 32 | 128 — the dq of
     ``attn_train_bwd_hd`` alone, bit-identical to it."""
-    _rows64(q, k, v, lse, dmo, dd)
-    D = _train_hd_width("attn_train_dq_hd", q)
-    BH, Nc, _ = q.shape
-    Ns = k.shape[1] if k.dim() == 3 else -1
-    if lse.shape != (BH, Nc) or dmo.shape != (BH, Nc, 2 * D) or dd.shape != (BH, Nc) or k.shape != (BH, Ns, D) \
-            or v.shape != k.shape or Ns <= 0:
-        raise ValueError("attn_train_dq_hd: bad shapes")
+    BH, Nc, Ns, D = _train_shapes("attn_train_dq_hd", None, q, k, v, (lse, "row"), (dmo, "wide"), (dd, "row"))
     DQ_ONLY_COUNTS["dq_only"] += 1
     dq = torch.empty_like(q)
     _call("mhada_attn_train_dq_hd", q, q.data_ptr(), k.data_ptr(), v.data_ptr(), lse.data_ptr(), dmo.data_ptr(),
@@ -1560,15 +1502,8 @@ def attn_train_fwd_bf16(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, x: to
     (csrc/attn_train_bf16.hip; fp32 accumulation and softmax): fp32 q, x (BH, Nc, 64); k, v (BH, Ns, 64)
     with v centred.  Returns fp32 out' (BH, Nc, 64), [M' | E2'] (BH, Nc, 128), lse2 (BH, Nc).  The bf16
     operand images live in a workspace freed after the call."""
-    _rows64(q, k, v, x)
-    BH, Nc, d = q.shape if q.dim() == 3 else (0, 0, 0)
-    Ns = k.shape[1] if k.dim() == 3 else -1
-    if d != 64 or k.shape != (BH, Ns, 64) or v.shape != k.shape or x.shape != q.shape or Ns <= 0:
-        raise ValueError(f"attn_train_fwd_bf16: bad shapes q{tuple(q.shape)} k{tuple(k.shape)} v{tuple(v.shape)} "
-                         f"x{tuple(x.shape)}")
-    out = torch.empty_like(q)
-    mo = torch.empty(BH, Nc, 128, device=q.device, dtype=torch.float32)
-    lse = torch.empty(BH, Nc, device=q.device, dtype=torch.float32)
+    BH, Nc, Ns, _ = _train_shapes("attn_train_fwd_bf16", 64, q, k, v, (x, "q"))
+    out, mo, lse = _train_fwd_out(q, 64)
     ws = _bf16_workspace(q, BH, Nc, Ns, False)
     BF16_TRAIN_COUNTS["fwd"] += 1
     _call("mhada_attn_train_fwd_bf16", q, q.data_ptr(), k.data_ptr(), v.data_ptr(), x.data_ptr(), out.data_ptr(),
@@ -1581,12 +1516,7 @@ def attn_train_bwd_bf16_prepass(q, k, v, dmo, mo) -> torch.Tensor:
     of the backward, written into a new workspace that ``attn_train_bwd_bf16_run`` consumes.  dmo is
     dead afterwards: a caller that drops it before the run keeps the peak memory lower
     (MHAdaAttnBf16Fn.backward)."""
-    _rows64(q, k, v, dmo, mo)
-    BH, Nc, d = q.shape if q.dim() == 3 else (0, 0, 0)
-    Ns = k.shape[1] if k.dim() == 3 else -1
-    if d != 64 or dmo.shape != (BH, Nc, 128) or mo.shape != dmo.shape or k.shape != (BH, Ns, 64) \
-            or v.shape != k.shape or Ns <= 0:
-        raise ValueError("attn_train_bwd_bf16: bad shapes")
+    BH, Nc, Ns, _ = _train_shapes("attn_train_bwd_bf16", 64, q, k, v, (dmo, "wide"), (mo, "wide"))
     ws = _bf16_workspace(q, BH, Nc, Ns, True)
     _call("mhada_attn_train_bwd_bf16", q, q.data_ptr(), k.data_ptr(), v.data_ptr(), None, dmo.data_ptr(),
           mo.data_ptr(), None, None, None, ws.data_ptr(), ws.numel(), BH, Nc, Ns, 1)
@@ -1596,13 +1526,10 @@ def attn_train_bwd_bf16_prepass(q, k, v, dmo, mo) -> torch.Tensor:
 def attn_train_bwd_bf16_run(q, k, v, lse, ws: torch.Tensor):
     """Phase 2 of ``mhada_attn_train_bwd_bf16``: the dQ and dK / dV' kernels on the workspace of
     ``attn_train_bwd_bf16_prepass`` (same q, k, v).  Returns fp32 dq (BH, Nc, 64), dk, dv (BH, Ns, 64)."""
-    _rows64(q, k, v, lse)
     _need_gpu(ws)
-    BH, Nc, d = q.shape if q.dim() == 3 else (0, 0, 0)
-    Ns = k.shape[1] if k.dim() == 3 else -1
-    if d != 64 or lse.shape != (BH, Nc) or k.shape != (BH, Ns, 64) or v.shape != k.shape or Ns <= 0 \
-            or ws.dtype != torch.uint8:
-        raise ValueError("attn_train_bwd_bf16: bad shapes")
+    BH, Nc, Ns, _ = _train_shapes("attn_train_bwd_bf16", 64, q, k, v, (lse, "row"))
+    if ws.dtype != torch.uint8:
+        raise ValueError("attn_train_bwd_bf16: bad shapes (the workspace is uint8)")
     dq = torch.empty_like(q)
     dk = torch.empty_like(k)
     dv = torch.empty_like(v)
