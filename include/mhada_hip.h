@@ -935,6 +935,57 @@ long long mhada_lpips_layer_work(int B, long long P, int C);
 int mhada_lpips_layer(const float* fa, const float* fb, const float* w, int B, long long P, int C, double* work,
                       long long work_doubles, double* out, mhada_stream_t stream);
 
+/* The InceptionV3 trunk of SIFID (SIFID/inception.py; csrc/conv2d.hip).  Added to ABI 18 WITHOUT a
+ * version bump (purely additive, found by symbol; see the _hd entries).  All tensors fp32 NHWC.
+ *
+ * mhada_conv2d: y[(b, oh, ow) * ldc + c_off + n] = act(scale[n] * conv(x, w)[b][oh][ow][n] + shift[n]),
+ * act = ReLU when relu != 0: torchvision's BasicConv2d with the eval-mode BatchNorm folded to two
+ * vectors by the caller (the scale is applied AFTER the convolution, not folded into w).  x:
+ * [B][H][W][Cin]; w: [Cout][KH][KW][Cin] (the OIHW filter permuted); zero padding (ph, pw); output
+ * size floor((H + 2 ph - KH) / stride) + 1 (and the same along W).  KH x KW one of 1x1, 3x3, 5x5, 1x7,
+ * 7x1, 1x3, 3x1; stride 1 | 2; 0 <= ph < KH, 0 <= pw < KW; Cin % 4 == 0 (a 3-channel image is padded
+ * to 4 by mhada_inception_input, its filters with zeros); any Cout.  Rows of y are ldc >= c_off + Cout
+ * floats apart: the branches of a Mixed block write their slices of one concat buffer.  Exact fp32
+ * products on the fp32 MFMA, one fp32 FMA chain per output over k = (kh, kw, c); an output's bits do not
+ * depend on the tile form the call takes.  A null pointer, a size <= 0, a geometry outside the list, x or
+ * w not 16-byte aligned, or 2^31 output (or input) pixels or more return MHADA_ERR_ARG before any launch.
+ *
+ * mhada_maxpool3s2: max_pool2d(3, 2) (no padding, floor) of x [B][H][W][C] into y[px * ldc + c_off + c];
+ * C, ldc, c_off multiples of 4, H, W >= 3.  mhada_avgpool3: avg_pool2d(3, 1, 1) with
+ * count_include_pad=True: the in-range taps added in row-major order, divided by 9 everywhere; y
+ * [B][H][W][C].  mhada_inception_input: x NCHW [B][3][H][W] -> y NHWC [B][H][W][4], channel 3 zero,
+ * v -> 2 v - 1 when normalize != 0 (inception.py:137-138). */
+int mhada_conv2d(const float* x, const float* w, const float* scale, const float* shift, float* y, int B, int H, int W,
+                 int Cin, int Cout, int KH, int KW, int stride, int ph, int pw, long long ldc, int c_off, int relu,
+                 mhada_stream_t stream);
+/* mhada_conv2d_stem: the trunk's first conv as a direct 3-channel kernel evaluated in fp64.  x: the NCHW
+ * image [B][3][H][W] (fp32; v -> 2 v - 1 in fp64 when normalize != 0); w: the packed filter [Cout][KH][KW][4]
+ * (channel 3 is not read); scale, shift: fp64 [Cout].  The fp32 operands' products, their sum and the affine
+ * are fp64, rounded to fp32 once at the store: the image SIFID's reference scale feeds is within 0.008 of a
+ * constant, and an fp32 chain would leave that constant's rounding noise on the content.  Geometry, ldc /
+ * c_off and the rejected arguments as for mhada_conv2d. */
+int mhada_conv2d_stem(const float* x, const float* w, const double* scale, const double* shift, float* y, int B, int H,
+                      int W, int Cout, int KH, int KW, int stride, int ph, int pw, long long ldc, int c_off, int relu,
+                      int normalize, mhada_stream_t stream);
+int mhada_maxpool3s2(const float* x, float* y, int B, int H, int W, int C, long long ldc, int c_off,
+                     mhada_stream_t stream);
+int mhada_avgpool3(const float* x, float* y, int B, int H, int W, int C, mhada_stream_t stream);
+int mhada_inception_input(const float* x, float* y, int B, int H, int W, int normalize, mhada_stream_t stream);
+
+/* The moments of SIFID (SIFID/sifid_score.py:185-205; csrc/sifid.hip) of the fp32 feature rows x [n][C]
+ * of one image, accumulated in fp64 in a fixed order (no atomics: repeated calls return the same bits).
+ * Added to ABI 18 WITHOUT a version bump (purely additive, found by symbol).  No workspace is needed.
+ *   mhada_sifid_stats: mean[c] = sum_i x[i][c] / n, ssq[c] = sum_i (x[i][c] - mean[c])^2 (two-pass).
+ *   mhada_sifid_cross: out[i][j] = sum_c (x1[i][c] - mean1[c]) (x2[j][c] - mean2[c]), fp64 [n1][n2].
+ *   mhada_sifid_cov:   out[p][q] = sum_i (x[i][p] - mean[p]) (x[i][q] - mean[q]), fp64 [C][C] (not
+ *                      divided by n - 1).
+ * A null pointer, a size <= 0, 2^31 rows or more (mhada_sifid_cross: n1 > 16 * 65535) return
+ * MHADA_ERR_ARG before any launch. */
+int mhada_sifid_stats(const float* x, long long n, int C, double* mean, double* ssq, mhada_stream_t stream);
+int mhada_sifid_cross(const float* x1, const double* mean1, long long n1, const float* x2, const double* mean2,
+                      long long n2, int C, double* out, mhada_stream_t stream);
+int mhada_sifid_cov(const float* x, const double* mean, long long n, int C, double* out, mhada_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -158,6 +158,14 @@ SIGNATURES = {
     "mhada_hist_u8": (_I, [_vp, _I, _I, _I, _c_ll, _I, _vp, _vp]),
     "mhada_lpips_layer_work": (_c_ll, [_I, _c_ll, _I]),
     "mhada_lpips_layer": (_I, [_vp, _vp, _vp, _I, _c_ll, _I, _vp, _c_ll, _vp, _vp]),
+    "mhada_conv2d": (_I, [_vp] * 5 + [_I] * 10 + [_c_ll, _I, _I, _vp]),
+    "mhada_conv2d_stem": (_I, [_vp] * 5 + [_I] * 9 + [_c_ll, _I, _I, _I, _vp]),
+    "mhada_maxpool3s2": (_I, [_vp, _vp, _I, _I, _I, _I, _c_ll, _I, _vp]),
+    "mhada_avgpool3": (_I, [_vp, _vp, _I, _I, _I, _I, _vp]),
+    "mhada_inception_input": (_I, [_vp, _vp, _I, _I, _I, _I, _vp]),
+    "mhada_sifid_stats": (_I, [_vp, _c_ll, _I, _vp, _vp, _vp]),
+    "mhada_sifid_cross": (_I, [_vp, _vp, _c_ll, _vp, _vp, _c_ll, _I, _vp, _vp]),
+    "mhada_sifid_cov": (_I, [_vp, _vp, _c_ll, _I, _vp, _vp]),
     # clips: B frames against one style, and the grouped batch-axis attention
     "mhada_attn_shared": (_I, [_vp] * 8 + [_I, _I, _I, _I, _I, _I, _vp]),
     "mhada_attn_split3_shared": (_I, [_vp] * 7 + [_I, _I, _I, _I, _vp]),

@@ -1,4 +1,4 @@
-"""Score stylised frames on the device: ten of the twelve numbers of the reference's result tables
+"""Score stylised frames on the device: the twelve numbers of the reference's result tables
 (eval.py, driven by exps_image.py; eight need no weights), on u8 frames [B][H][W][3] in device memory — what
 ``VideoStylizer.stylize_u8`` returns and what eval.py reads back from the PNG it wrote.
 
@@ -7,18 +7,26 @@
   moment / uniformity / entropy    eval.py:111-164 on the gray image mhada_hist_u8 + host fp64
   gram(a, b, vgg)                  gram_loss (eval.py:78-108)        HIP VGG19, mhada_gemm_tn, mhada_feat_stats
   lpips(a, b, vgg16, lins)         lpips.LPIPS(net="vgg") (eval.py:22)  HIP VGG16, mhada_lpips_layer
+  sifid(a, b, inception)           calculate_sifid_given_paths (eval.py:226-274)  HIP InceptionV3, mhada_sifid_*
   score(stylized, content, style)  the CSV row of exps_image.py:90-123, one value per image
 
 LPIPS is here for callers who hand in a ``network.VGG16`` with ImageNet weights and the five linear
 vectors of an lpips checkout (``lpips_weights``): the package ships and fetches no weights, so there
 is no default, and without ``lpips=`` the two LPIPS keys are absent from ``score``, not NaN.  SIFID
-needs Inception and is not here.  Frames may have padded rows; CPU tensors raise (no host fallback).  The
+follows the same rule: the caller hands in a ``network.InceptionV3`` with ImageNet weights
+(``InceptionV3.load_torchvision``), and without ``sifid=`` its two keys are absent.  Frames may have padded rows; CPU tensors raise (no host fallback).  The
 histogram metrics are finalised on the host from the 4 KB of exact counts, in numpy fp64 as the
 reference computes them; the ``*_from_counts`` functions are that arithmetic and need no GPU.
 
 The SSIM is held to the fp64 value of the reference's definition, not to its fp32 result: with
 C2 = 0.03^2 applied to [0, 255] values the fp32 evaluation is rounding noise on smooth regions
 (DESIGN.md, "SSIM").
+
+SIFID's input scale: exps_image.py hands SIFID PNG files, for which matplotlib's imread already returns
+fp32 in [0, 1]; sifid_score.py:104 then divides by 255 again, so the trunk sees 2 (v / 255 / 255) - 1 in
+[-1, -0.992].  That is the number in the reference's tables and the default here (``input_scale=
+"reference"``); ``"unit"`` is v / 255, what a JPEG file gets there and what SIFID was designed for
+(DESIGN.md, "SIFID").
 """
 from __future__ import annotations
 
@@ -32,6 +40,9 @@ from . import ops
 SCORE_KEYS = ("ssim_content", "kl_c", "ssim_style", "kl_s", "gram", "moment", "uniformity", "entropy")
 SCORE_KEYS_LPIPS = ("lpips_content", "ssim_content", "kl_c", "lpips_style", "ssim_style", "kl_s", "gram", "moment",
                     "uniformity", "entropy")  # the reference's CSV order, without sifid
+SCORE_KEYS_FULL = ("lpips_content", "ssim_content", "sifid_content", "kl_c", "lpips_style", "ssim_style", "sifid_style",
+                   "kl_s", "gram", "moment", "uniformity", "entropy")  # exps_image.py:108-125
+_SIFID_DIMS = {64: 0, 192: 1, 768: 2, 2048: 3}  # inception.py:14-19
 _VGG_LAYERS = tuple(f"relu{i}_1" for i in range(1, 6))
 _LPIPS_CHNS = (64, 128, 256, 512, 512)  # lpips.py:91
 
@@ -79,6 +90,54 @@ def entropy_from_counts(gray_counts) -> np.ndarray:
     """average_entropy (eval.py:149-164): -sum p log2 p (every p > 0 after the + 1)."""
     _, hist_p = _gray_hist(gray_counts)
     return -(hist_p * np.log2(hist_p)).sum(axis=-1)
+
+
+def frechet_from_moments(mu1, tr1: float, n1: int, mu2, tr2: float, n2: int, cross=None, scatter1=None,
+                         scatter2=None) -> float:
+    """calculate_frechet_distance (sifid_score.py:128-182), d^2 = |mu1 - mu2|^2 + tr S1 + tr S2 - 2 tr sqrt(S1 S2),
+    from fp64 moments of the two sets of feature rows (n1, n2 rows): ``mu`` the means [C], ``tr`` the
+    centred sums of squares added over the channels (tr S = tr / (n - 1), np.cov's ddof 1), and either
+      cross    = Xc1 Xc2^T [n1][n2]: the non-zero eigenvalues of S1 S2 are the squared singular values of
+                 M = cross / sqrt((n1 - 1)(n2 - 1)), so tr sqrt(S1 S2) is M's nuclear norm — exact whatever the
+                 rank, where sqrtm of the singular product S1 S2 returns a complex matrix with noise; or
+      scatter1 = Xc1^T Xc1 and scatter2 [C][C]: sum sqrt(max(lambda, 0)) of eigvalsh(S1^(1/2) S2 S1^(1/2)).
+    numpy fp64, no scipy, no GPU."""
+    if n1 < 2 or n2 < 2:
+        raise ValueError(f"frechet_from_moments: at least 2 feature rows per image are needed (np.cov of fewer is NaN), "
+                         f"got {n1} and {n2}")
+    mu1, mu2 = np.asarray(mu1, np.float64), np.asarray(mu2, np.float64)
+    if mu1.shape != mu2.shape or mu1.ndim != 1:
+        raise ValueError(f"frechet_from_moments: the means must be two [C] vectors, got {mu1.shape} and {mu2.shape}")
+    if cross is not None:
+        cross = np.asarray(cross, np.float64)
+        if cross.shape != (n1, n2):
+            raise ValueError(f"frechet_from_moments: cross must be [{n1}][{n2}], got {cross.shape}")
+        tr_covmean = np.linalg.svd(cross / np.sqrt(float(n1 - 1) * float(n2 - 1)), compute_uv=False).sum()
+    elif scatter1 is not None and scatter2 is not None:
+        s1, s2 = np.asarray(scatter1, np.float64) / (n1 - 1), np.asarray(scatter2, np.float64) / (n2 - 1)
+        if s1.shape != (mu1.size, mu1.size) or s2.shape != s1.shape:
+            raise ValueError(f"frechet_from_moments: the scatter matrices must be [C][C], got {s1.shape} and {s2.shape}")
+        lam, vec = np.linalg.eigh((s1 + s1.T) / 2)
+        root = (vec * np.sqrt(np.maximum(lam, 0.0))) @ vec.T
+        inner = root @ ((s2 + s2.T) / 2) @ root
+        tr_covmean = np.sqrt(np.maximum(np.linalg.eigvalsh((inner + inner.T) / 2), 0.0)).sum()
+    else:
+        raise ValueError("frechet_from_moments: pass cross=, or scatter1= and scatter2=")
+    diff = mu1 - mu2
+    return float(diff.dot(diff) + tr1 / (n1 - 1) + tr2 / (n2 - 1) - 2.0 * tr_covmean)
+
+
+def sifid_input_levels(input_scale: str = "reference") -> np.ndarray:
+    """The fp32 trunk input of each of the 256 byte values, with the reference's own fp32 operations
+    (sifid_score.py:97-104): "reference" = imread's v / 255 of a PNG (fp32) divided by 255 again; "unit" =
+    v / 255, what a JPEG file gets there."""
+    if input_scale not in ("reference", "unit"):
+        raise ValueError(f"sifid: input_scale must be 'reference' or 'unit', got {input_scale!r}")
+    v = np.arange(256, dtype=np.float32)
+    v /= np.float32(255)
+    if input_scale == "reference":
+        v /= np.float32(255)
+    return v
 
 
 # ---- device metrics ------------------------------------------------------------------------
@@ -211,12 +270,86 @@ def lpips(a_u8: torch.Tensor, b_u8: torch.Tensor, vgg16=None, lins=None, bgr: bo
     return lpips_from_features(vgg16_features(a_u8, vgg16, bgr), vgg16_features(b_u8, vgg16, bgr), lins, per_layer)
 
 
+def _sifid_block(inception, dims: int) -> int:
+    if dims not in _SIFID_DIMS:
+        raise ValueError(f"sifid: dims must be one of {sorted(_SIFID_DIMS)}, got {dims!r}")
+    if inception is None:
+        raise ValueError("sifid: pass inception=network.InceptionV3() with its weights loaded (load_torchvision)")
+    blk = _SIFID_DIMS[dims]
+    if blk > inception.last_needed_block:
+        raise ValueError(f"sifid: dims={dims} needs block {blk}, the InceptionV3 was built up to block "
+                         f"{inception.last_needed_block}")
+    return blk
+
+
+@torch.no_grad()
+def sifid_features(frames_u8: torch.Tensor, inception, dims: int = 2048, input_scale: str = "reference",
+                   bgr: bool = True) -> torch.Tensor:
+    """The Inception feature map of block ``dims`` of u8 frames as contiguous NHWC fp32 [B][H'][W'][dims]:
+    the bytes go through the 256-entry table of ``sifid_input_levels`` (so the trunk's input is the
+    reference's bit for bit), RGB order, then the HIP InceptionV3, which applies 2 x - 1."""
+    blk = _sifid_block(inception, dims)
+    levels = sifid_input_levels(input_scale)
+    frames = ops._u8_input(frames_u8, "sifid")
+    lut = torch.from_numpy(levels).to(frames.device)
+    x = lut[frames.long()]  # [B][H][W][3], padded rows dropped by the view's shape
+    if bgr:
+        x = x.flip(-1)
+    saved = inception.output_blocks
+    inception.output_blocks = [blk]
+    try:
+        feat = inception(x.permute(0, 3, 1, 2))[0]
+    finally:
+        inception.output_blocks = saved
+    return feat.permute(0, 2, 3, 1).contiguous()
+
+
+@torch.no_grad()
+def sifid_from_features(fa: torch.Tensor, fb: torch.Tensor) -> np.ndarray:
+    """calculate_activation_statistics + calculate_frechet_distance (sifid_score.py:128-205) per image pair
+    from two NHWC feature maps [B][H'][W'][C] (the two may differ in H', W'): float64 [B].  The moments are
+    fp64 on the device (mhada_sifid_*); the cross form when an image has fewer positions than channels,
+    else the covariance form."""
+    if fa.dim() != 4 or fb.dim() != 4 or fa.shape[0] != fb.shape[0] or fa.shape[3] != fb.shape[3]:
+        raise ValueError(f"sifid: two NHWC feature batches of one B and C, got {tuple(fa.shape)} and {tuple(fb.shape)}")
+    B, C = fa.shape[0], fa.shape[3]
+    n1, n2 = fa.shape[1] * fa.shape[2], fb.shape[1] * fb.shape[2]
+    if n1 < 2 or n2 < 2:
+        raise ValueError(f"sifid: a feature map with fewer than 2 positions has no covariance (got {n1} and {n2}); "
+                         "the images are too small for this dims")
+    out = np.zeros(B)
+    for i in range(B):
+        x1, x2 = fa[i].reshape(n1, C), fb[i].reshape(n2, C)
+        (m1, q1), (m2, q2) = ops.sifid_stats(x1), ops.sifid_stats(x2)
+        kw = {}
+        if min(n1, n2) < C:
+            kw["cross"] = ops.sifid_cross(x1, m1, x2, m2).cpu().numpy()
+        else:
+            kw["scatter1"], kw["scatter2"] = ops.sifid_cov(x1, m1).cpu().numpy(), ops.sifid_cov(x2, m2).cpu().numpy()
+        out[i] = frechet_from_moments(m1.cpu().numpy(), float(q1.cpu().numpy().sum()), n1, m2.cpu().numpy(),
+                                      float(q2.cpu().numpy().sum()), n2, **kw)
+    return out
+
+
+def sifid(a_u8: torch.Tensor, b_u8: torch.Tensor, inception=None, dims: int = 2048, input_scale: str = "reference",
+          bgr: bool = True) -> np.ndarray:
+    """calculate_sifid_given_paths (eval.py:226-274, sifid_score.py:222-247) per image pair -> float64 [B]; the
+    two batches may differ in H x W.  ``inception``: a ``network.InceptionV3`` on the frames' device with
+    ImageNet weights (``load_torchvision``); there is no default.  ``input_scale``: see the module text."""
+    _sifid_block(inception, dims)
+    sifid_input_levels(input_scale)  # before any launch
+    return sifid_from_features(sifid_features(a_u8, inception, dims, input_scale, bgr),
+                               sifid_features(b_u8, inception, dims, input_scale, bgr))
+
+
 def score(stylized_u8: torch.Tensor, content_u8: torch.Tensor, style_u8: torch.Tensor, bgr: bool = True,
-          vgg=None, lpips=None) -> Dict[str, np.ndarray]:
+          vgg=None, lpips=None, sifid=None) -> Dict[str, np.ndarray]:
     """The columns of exps_image.py's CSV for a batch, float64 [B] per key: the weight-free SCORE_KEYS, or
     with ``lpips=(vgg16, lins)`` (as in ``lpips``) the ten SCORE_KEYS_LPIPS in the CSV's order; the stylised
-    frames' VGG16 features are computed once for both LPIPS columns.  ``vgg`` as in ``gram``; without one
-    the ``gram`` key cannot be computed and the call raises."""
+    frames' VGG16 features are computed once for both LPIPS columns.  ``sifid=inception`` (as in ``sifid``,
+    dims 2048, the reference's input scale) adds ``sifid_content`` and ``sifid_style``, the stylised frames'
+    trunk pass shared by both; with ``lpips=`` as well the row is the twelve SCORE_KEYS_FULL in the CSV's
+    order.  ``vgg`` as in ``gram``; without one the ``gram`` key cannot be computed and the call raises."""
     if vgg is None:
         raise ValueError("score: pass vgg=network.VGG19() with its weights loaded (needed for 'gram')")
     lp = {}
@@ -226,6 +359,12 @@ def score(stylized_u8: torch.Tensor, content_u8: torch.Tensor, style_u8: torch.T
         fs = vgg16_features(stylized_u8, vgg16, bgr)
         lp = {"lpips_content": lpips_from_features(fs, vgg16_features(content_u8, vgg16, bgr), lins),
               "lpips_style": lpips_from_features(fs, vgg16_features(style_u8, vgg16, bgr), lins)}
+    sf = {}
+    if sifid is not None:
+        _sifid_block(sifid, 2048)  # before any launch
+        fs = sifid_features(stylized_u8, sifid, bgr=bgr)
+        sf = {"sifid_content": sifid_from_features(fs, sifid_features(content_u8, sifid, bgr=bgr)),
+              "sifid_style": sifid_from_features(fs, sifid_features(style_u8, sifid, bgr=bgr))}
     hs = _hist(stylized_u8, bgr)
     out = {
         "ssim_content": ssim(stylized_u8, content_u8, "none").double().cpu().numpy(),
@@ -238,7 +377,8 @@ def score(stylized_u8: torch.Tensor, content_u8: torch.Tensor, style_u8: torch.T
         "entropy": entropy_from_counts(hs[:, 3]),
     }
     assert tuple(out) == SCORE_KEYS
-    if lp:
+    if lp or sf:
         out.update(lp)
-        out = {k: out[k] for k in SCORE_KEYS_LPIPS}
+        out.update(sf)
+        out = {k: out[k] for k in SCORE_KEYS_FULL if k in out}
     return out

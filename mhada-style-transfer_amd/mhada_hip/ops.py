@@ -1982,6 +1982,193 @@ def lpips_layer(fa: torch.Tensor, fb: torch.Tensor, w: torch.Tensor) -> torch.Te
     return out
 
 
+# ---- InceptionV3 trunk of SIFID (csrc/conv2d.hip) and its moments (csrc/sifid.hip) ---------------
+_CONV2D_KERNELS = ((1, 1), (3, 3), (5, 5), (1, 7), (7, 1), (1, 3), (3, 1))
+
+
+def _nhwc_f32(x: torch.Tensor, what: str) -> torch.Tensor:
+    _need_gpu(x)
+    if x.dtype != torch.float32 or x.dim() != 4 or not x.is_contiguous() or x.numel() == 0:
+        raise ValueError(f"{what}: contiguous fp32 NHWC [B][H][W][C], got {x.dtype} {tuple(x.shape)}")
+    return x
+
+
+def conv2d_pack_weight(w: torch.Tensor) -> torch.Tensor:
+    """An OIHW filter as ``mhada_conv2d`` reads it: fp32 [Cout][KH][KW][Cin'] with Cin' = Cin rounded up
+    to a multiple of 4, the added channels zero (they meet the zero channel of ``inception_input``)."""
+    if w.dim() != 4:
+        raise ValueError(f"conv2d_pack_weight: OIHW filter, got {tuple(w.shape)}")
+    w = w.detach().to(torch.float32).permute(0, 2, 3, 1)
+    pad = -w.shape[3] % 4
+    if pad:
+        w = torch.nn.functional.pad(w, (0, pad))
+    return w.contiguous()
+
+
+def conv2d_out_hw(H: int, W: int, kernel, stride: int, padding):
+    return (H + 2 * padding[0] - kernel[0]) // stride + 1, (W + 2 * padding[1] - kernel[1]) // stride + 1
+
+
+def conv2d(x: torch.Tensor, w: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor, stride: int = 1,
+           padding=(0, 0), relu: bool = True, out: Optional[torch.Tensor] = None, c_off: int = 0) -> torch.Tensor:
+    """``mhada_conv2d``: act(scale * conv(x, w) + shift) of fp32 NHWC x [B][H][W][Cin] with a packed filter
+    w [Cout][KH][KW][Cin] (``conv2d_pack_weight``), zero padding (ph, pw), stride 1 | 2.  ``out``
+    [B][Ho][Wo][ldc] with ``c_off``: the result goes into channels c_off .. c_off + Cout of that buffer
+    (the concat buffer of a Mixed block); without it a new [B][Ho][Wo][Cout] tensor."""
+    x = _nhwc_f32(x, "conv2d")
+    _need_gpu(x, w, scale, shift, out)
+    B, H, W, Cin = x.shape
+    if w.dtype != torch.float32 or w.dim() != 4 or not w.is_contiguous() or w.shape[3] != Cin:
+        raise ValueError(f"conv2d: packed fp32 filter [Cout][KH][KW][{Cin}] (conv2d_pack_weight), got {tuple(w.shape)}")
+    Cout, KH, KW, _ = w.shape
+    if (KH, KW) not in _CONV2D_KERNELS:
+        raise ValueError(f"conv2d: kernel {KH}x{KW} is not one of {_CONV2D_KERNELS}")
+    for v, name in ((scale, "scale"), (shift, "shift")):
+        if v.dtype != torch.float32 or tuple(v.shape) != (Cout,) or not v.is_contiguous():
+            raise ValueError(f"conv2d: {name} must be contiguous fp32 [{Cout}]")
+    ph, pw = padding
+    Ho, Wo = conv2d_out_hw(H, W, (KH, KW), stride, (ph, pw))
+    if Ho <= 0 or Wo <= 0:
+        raise ValueError(f"conv2d: a {H}x{W} input is smaller than the {KH}x{KW} kernel")
+    if out is None:
+        if c_off:
+            raise ValueError("conv2d: c_off needs out=")
+        out = torch.empty(B, Ho, Wo, Cout, device=x.device, dtype=torch.float32)
+    elif out.dtype != torch.float32 or out.dim() != 4 or not out.is_contiguous() or tuple(out.shape[:3]) != (B, Ho, Wo):
+        raise ValueError(f"conv2d: out must be contiguous fp32 [{B}][{Ho}][{Wo}][ldc], got {tuple(out.shape)}")
+    ldc = out.shape[3]
+    if c_off < 0 or c_off + Cout > ldc:
+        raise ValueError(f"conv2d: channels {c_off}..{c_off + Cout} do not fit ldc {ldc}")
+    _call("mhada_conv2d", x, x.data_ptr(), w.data_ptr(), scale.data_ptr(), shift.data_ptr(), out.data_ptr(), B, H, W, Cin,
+          Cout, KH, KW, int(stride), int(ph), int(pw), ldc, int(c_off), int(bool(relu)))
+    return out
+
+
+def conv2d_stem(x: torch.Tensor, w: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor, stride: int = 1,
+                padding=(0, 0), relu: bool = True, normalize: bool = True, out: Optional[torch.Tensor] = None,
+                c_off: int = 0) -> torch.Tensor:
+    """``mhada_conv2d_stem``: the trunk's first conv, direct and in fp64, rounded to fp32 once: x the NCHW fp32
+    image [B][3][H][W] (2 x - 1 applied in fp64 when ``normalize``), w the packed filter [Cout][KH][KW][4]
+    (``conv2d_pack_weight`` of a 3-channel filter), scale / shift fp64 [Cout] -> NHWC [B][Ho][Wo][Cout], or into
+    ``out`` at ``c_off`` as ``conv2d``."""
+    _need_gpu(x, w, scale, shift, out)
+    if x.dtype != torch.float32 or x.dim() != 4 or x.shape[1] != 3 or x.numel() == 0:
+        raise ValueError(f"conv2d_stem: fp32 NCHW [B][3][H][W], got {x.dtype} {tuple(x.shape)}")
+    x = x.contiguous()
+    B, _, H, W = x.shape
+    if w.dtype != torch.float32 or w.dim() != 4 or not w.is_contiguous() or w.shape[3] != 4:
+        raise ValueError(f"conv2d_stem: packed fp32 filter [Cout][KH][KW][4] (conv2d_pack_weight), got {tuple(w.shape)}")
+    Cout, KH, KW, _ = w.shape
+    if (KH, KW) not in _CONV2D_KERNELS:
+        raise ValueError(f"conv2d_stem: kernel {KH}x{KW} is not one of {_CONV2D_KERNELS}")
+    for v, name in ((scale, "scale"), (shift, "shift")):
+        if v.dtype != torch.float64 or tuple(v.shape) != (Cout,) or not v.is_contiguous():
+            raise ValueError(f"conv2d_stem: {name} must be contiguous fp64 [{Cout}]")
+    ph, pw = padding
+    Ho, Wo = conv2d_out_hw(H, W, (KH, KW), stride, (ph, pw))
+    if Ho <= 0 or Wo <= 0:
+        raise ValueError(f"conv2d_stem: a {H}x{W} input is smaller than the {KH}x{KW} kernel")
+    if out is None:
+        if c_off:
+            raise ValueError("conv2d_stem: c_off needs out=")
+        out = torch.empty(B, Ho, Wo, Cout, device=x.device, dtype=torch.float32)
+    elif out.dtype != torch.float32 or out.dim() != 4 or not out.is_contiguous() or tuple(out.shape[:3]) != (B, Ho, Wo):
+        raise ValueError(f"conv2d_stem: out must be contiguous fp32 [{B}][{Ho}][{Wo}][ldc], got {tuple(out.shape)}")
+    ldc = out.shape[3]
+    if c_off < 0 or c_off + Cout > ldc:
+        raise ValueError(f"conv2d_stem: channels {c_off}..{c_off + Cout} do not fit ldc {ldc}")
+    _call("mhada_conv2d_stem", x, x.data_ptr(), w.data_ptr(), scale.data_ptr(), shift.data_ptr(), out.data_ptr(), B, H, W,
+          Cout, KH, KW, int(stride), int(ph), int(pw), ldc, int(c_off), int(bool(relu)), int(bool(normalize)))
+    return out
+
+
+def maxpool3s2(x: torch.Tensor, out: Optional[torch.Tensor] = None, c_off: int = 0) -> torch.Tensor:
+    """``mhada_maxpool3s2``: max_pool2d(3, 2) of fp32 NHWC x; ``out`` / ``c_off`` as in ``conv2d``."""
+    x = _nhwc_f32(x, "maxpool3s2")
+    B, H, W, C = x.shape
+    if H < 3 or W < 3:
+        raise ValueError(f"maxpool3s2: a {H}x{W} input is smaller than the 3x3 window")
+    Ho, Wo = (H - 3) // 2 + 1, (W - 3) // 2 + 1
+    if out is None:
+        if c_off:
+            raise ValueError("maxpool3s2: c_off needs out=")
+        out = torch.empty(B, Ho, Wo, C, device=x.device, dtype=torch.float32)
+    elif out.dtype != torch.float32 or out.dim() != 4 or not out.is_contiguous() or tuple(out.shape[:3]) != (B, Ho, Wo):
+        raise ValueError(f"maxpool3s2: out must be contiguous fp32 [{B}][{Ho}][{Wo}][ldc], got {tuple(out.shape)}")
+    _need_gpu(x, out)
+    _call("mhada_maxpool3s2", x, x.data_ptr(), out.data_ptr(), B, H, W, C, out.shape[3], int(c_off))
+    return out
+
+
+def avgpool3(x: torch.Tensor) -> torch.Tensor:
+    """``mhada_avgpool3``: avg_pool2d(3, 1, 1), count_include_pad=True (/ 9 everywhere), fp32 NHWC."""
+    x = _nhwc_f32(x, "avgpool3")
+    out = torch.empty_like(x)
+    _call("mhada_avgpool3", x, x.data_ptr(), out.data_ptr(), *x.shape)
+    return out
+
+
+def inception_input(x: torch.Tensor, normalize: bool = True) -> torch.Tensor:
+    """``mhada_inception_input``: NCHW fp32 [B][3][H][W] -> NHWC [B][H][W][4] (channel 3 zero), 2 x - 1
+    when ``normalize`` (inception.py:137-138)."""
+    _need_gpu(x)
+    if x.dtype != torch.float32 or x.dim() != 4 or x.shape[1] != 3 or x.numel() == 0:
+        raise ValueError(f"inception_input: fp32 NCHW [B][3][H][W], got {x.dtype} {tuple(x.shape)}")
+    x = x.contiguous()
+    B, _, H, W = x.shape
+    out = torch.empty(B, H, W, 4, device=x.device, dtype=torch.float32)
+    _call("mhada_inception_input", x, x.data_ptr(), out.data_ptr(), B, H, W, int(bool(normalize)))
+    return out
+
+
+def _feature_rows(x: torch.Tensor, what: str) -> torch.Tensor:
+    _need_gpu(x)
+    if x.dtype != torch.float32 or x.dim() != 2 or not x.is_contiguous() or x.numel() == 0:
+        raise ValueError(f"{what}: contiguous fp32 feature rows [n][C], got {x.dtype} {tuple(x.shape)}")
+    return x
+
+
+def sifid_stats(x: torch.Tensor):
+    """``mhada_sifid_stats``: (mean [C], centred sum of squares [C]) in fp64 of fp32 rows x [n][C]."""
+    x = _feature_rows(x, "sifid_stats")
+    n, C = x.shape
+    mean = torch.empty(C, device=x.device, dtype=torch.float64)
+    ssq = torch.empty(C, device=x.device, dtype=torch.float64)
+    _call("mhada_sifid_stats", x, x.data_ptr(), n, C, mean.data_ptr(), ssq.data_ptr())
+    return mean, ssq
+
+
+def _check_mean(mean: torch.Tensor, C: int, what: str) -> None:
+    if mean.dtype != torch.float64 or tuple(mean.shape) != (C,) or not mean.is_contiguous():
+        raise ValueError(f"{what}: mean must be contiguous fp64 [{C}]")
+
+
+def sifid_cross(x1: torch.Tensor, mean1: torch.Tensor, x2: torch.Tensor, mean2: torch.Tensor) -> torch.Tensor:
+    """``mhada_sifid_cross``: the centred cross product Xc1 Xc2^T, fp64 [n1][n2]."""
+    x1, x2 = _feature_rows(x1, "sifid_cross"), _feature_rows(x2, "sifid_cross")
+    _need_gpu(x1, mean1, x2, mean2)
+    C = x1.shape[1]
+    if x2.shape[1] != C:
+        raise ValueError(f"sifid_cross: the rows differ in width, {C} and {x2.shape[1]}")
+    _check_mean(mean1, C, "sifid_cross")
+    _check_mean(mean2, C, "sifid_cross")
+    out = torch.empty(x1.shape[0], x2.shape[0], device=x1.device, dtype=torch.float64)
+    _call("mhada_sifid_cross", x1, x1.data_ptr(), mean1.data_ptr(), x1.shape[0], x2.data_ptr(), mean2.data_ptr(),
+          x2.shape[0], C, out.data_ptr())
+    return out
+
+
+def sifid_cov(x: torch.Tensor, mean: torch.Tensor) -> torch.Tensor:
+    """``mhada_sifid_cov``: the centred scatter matrix Xc^T Xc, fp64 [C][C] (np.cov times n - 1)."""
+    x = _feature_rows(x, "sifid_cov")
+    _need_gpu(x, mean)
+    n, C = x.shape
+    _check_mean(mean, C, "sifid_cov")
+    out = torch.empty(C, C, device=x.device, dtype=torch.float64)
+    _call("mhada_sifid_cov", x, x.data_ptr(), mean.data_ptr(), n, C, out.data_ptr())
+    return out
+
+
 # ---- training path (fp32, NHWC): backward helpers (include/mhada_hip.h) ------------------
 def gemm_tn(a: torch.Tensor, b: torch.Tensor, M: int, N: int, K: int, lda: int, ldb: int = 0,
             b_mode: int = A_ROWS, img=(0, 0, 0), pad: int = 0, colsum: bool = False, nb: int = 1,

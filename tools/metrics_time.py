@@ -8,6 +8,11 @@ Then the LPIPS distance head, mhada_lpips_layer, on the five tap shapes of VGG16
 non-negative NHWC features), beside the same expression written with torch ops on the same device tensors
 (lpips/lpips.py:139-147 on the NHWC storage), under the same protocol; the two results are compared first.
 
+Then SIFID at 512^2 (B = 1, random weights: the time does not depend on the values), dims 2048 and 64: the
+HIP InceptionV3 trunk alone (device events), the same modules run by aten on the device (informative; "not
+measured" if aten's conv fails here), and the whole metrics.sifid call of two frames, trunk passes, moment
+kernels, copies and the host's SVD / eigenvalues included (wall clock around a synchronised call).
+
     python tools/metrics_time.py [rounds]
 """
 import os
@@ -73,6 +78,53 @@ def time_lpips(rounds):
                   f"{nbytes / 1e6:.2f} MB read once, {nbytes / (t * 1e-3) / 1e9:.1f} GB/s of that")
 
 
+def time_sifid(rounds):
+    import time
+
+    import network
+    from mhada_hip import metrics
+    g = torch.Generator().manual_seed(7)
+    a = torch.randint(0, 256, (1, 512, 512, 3), generator=g, dtype=torch.uint8).to("cuda")
+    b = torch.randint(0, 256, (1, 512, 512, 3), generator=g, dtype=torch.uint8).to("cuda")
+    x = torch.rand(1, 3, 512, 512, generator=g).to("cuda")
+    for dims, blk in ((2048, 3), (64, 0)):
+        inc = network.InceptionV3([blk]).to("cuda")
+
+        def aten():
+            y = 2 * x - 1
+            for block in inc.blocks:
+                y = block(y)
+            return y
+
+        cand = {"HIP trunk": lambda: inc(x), "HIP trunk (again)": lambda: inc(x)}
+        try:
+            with torch.no_grad():
+                aten()
+            torch.cuda.synchronize()
+            cand.update({"aten trunk": aten, "aten trunk (again)": aten})
+        except Exception as e:  # informative only
+            print(f"SIFID dims {dims}: aten trunk not measured ({type(e).__name__})")
+        ts = {n: [] for n in cand}
+        wall = []
+        with torch.no_grad():
+            for fn in cand.values():  # warm-up
+                fn()
+            metrics.sifid(a, b, inc, dims=dims)
+            torch.cuda.synchronize()
+            for _ in range(rounds):
+                for n, fn in cand.items():
+                    ts[n].append(dev_ms(fn))
+                t0 = time.perf_counter()
+                metrics.sifid(a, b, inc, dims=dims)
+                torch.cuda.synchronize()
+                wall.append((time.perf_counter() - t0) * 1e3)
+        print(f"SIFID dims {dims}: 1 x 3 x 512 x 512, {rounds} interleaved rounds", flush=True)
+        for n in cand:
+            print(f"    {n:20s} {median(ts[n]):9.3f} ms  (min {min(ts[n]):.3f} max {max(ts[n]):.3f})")
+        print(f"    {'metrics.sifid (wall)':20s} {median(wall):9.3f} ms  (min {min(wall):.3f} max {max(wall):.3f})  two frames, "
+              "host finaliser included")
+
+
 def main():
     rounds = int(sys.argv[1]) if len(sys.argv) > 1 else 25
     for name, B, H, W in SHAPES:
@@ -95,6 +147,7 @@ def main():
             print(f"    {n:18s} {t * 1e3:9.1f} us  (min {min(ts[n]) * 1e3:.1f} max {max(ts[n]) * 1e3:.1f})  "
                   f"{nbytes / 1e6:.2f} MB read, {nbytes / (t * 1e-3) / 1e9:.1f} GB/s")
     time_lpips(rounds)
+    time_sifid(rounds)
 
 
 if __name__ == "__main__":
